@@ -1,6 +1,12 @@
 """Headline benchmark: Z3 encode points/s + st_contains join pairs/s on MI355X (BASELINE.json).
 
   python bench.py [--gpus N --steps K --warmup W]           (N > 1: launched by torch.distributed.run)
+  python bench.py --full [...]                              every leg below beside the headline
+  python bench.py --dump-outputs DIR [...]                  the last timed step's keys as DIR/*.npy
+
+A plain run generates the points, warms up, times K steps of the headline and prints the line;
+everything else described here (the join, the extra kernels, the sorted table, the box's copy rate,
+the CPU baselines and the oracle parity samples) runs only with --full.
 
 A step of the headline is one pass of Z3IndexKeySpace.toIndexKey's batch form (BinnedTime(week) +
 Z3SFC.index) over the rank's resident 1B-point shard (BASELINE configs[1]); `value` = points of all
@@ -51,7 +57,19 @@ def parse():
     p.add_argument("--join-grid", default="80x40", help="synthetic county grid (experiments)")
     p.add_argument("--no-gather", action="store_true", help="skip the join's result gather to rank 0")
     p.add_argument("--join-sorted", action="store_true", help="experiment: points pre-sorted by latitude")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="every leg beside the headline: the join, the extra kernels, the sorted table, the CPU "
+                        "baselines, the oracle parity samples and the box's copy rate (a plain run times the "
+                        "Z3 encode alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last Z3 encode step left (bin, z) to DIR/*.npy")
+    a = p.parse_args()
+    legs = set(a.only.split(",")) if a.only else set()
+    if not a.full and legs - {"z3"}:
+        p.error("--only %s needs --full (a plain run times the Z3 encode alone)" % a.only)
+    if a.dump_outputs and legs and "z3" not in legs:
+        p.error("--dump-outputs writes the Z3 encode's keys: --only must include z3")
+    return a
 
 
 class Dist:
@@ -137,6 +155,33 @@ def gen_points(ctx, n, base, box, x, y, t):
     from geomesa_amd import _lib
     _lib.check(ctx.lib.gm_gen_points(ctx.handle, SEED, n, base, box[0], box[2], box[1], box[3], T2020, T2021,
                                      _lib.ptr(x), _lib.ptr(y), _lib.ptr(t)), "gm_gen_points")
+
+
+DUMP_ROWS = 1 << 21            # rows of a dump: 20 B each, 40 MB in all
+DUMP_SEED = 20200601
+
+
+def dump_rows(n):
+    """The rows a dump holds: all n, or DUMP_ROWS of them drawn once from a seeded host generator and
+    sorted (the same rows in every run and every build)."""
+    import torch
+    if n <= DUMP_ROWS:
+        return torch.arange(n, dtype=torch.int64)
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    return torch.sort(torch.randint(0, n, (DUMP_ROWS,), dtype=torch.int64, generator=g)).values
+
+
+def dump_outputs(d, b, z):
+    """--dump-outputs: the keys the last timed step wrote for dump_rows(N), as DIR/<name>.npy.
+    bin (int16) is exact in float32; z (63 bits) is split into its high and low 32 bits, each exact
+    in float64: z = z_hi32 * 2**32 + z_lo32."""
+    rows = dump_rows(b.numel()).to(b.device)
+    hb = b[rows].cpu().numpy()
+    hz = z[rows].cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "bin.npy"), hb.astype(np.float32))
+    np.save(os.path.join(d, "z_hi32.npy"), (hz >> 32).astype(np.float64))
+    np.save(os.path.join(d, "z_lo32.npy"), (hz & 0xFFFFFFFF).astype(np.float64))
 
 
 def load_pmc(name, n):
@@ -886,6 +931,9 @@ def main():
     dist = Dist(a.gpus)
     ctx = _lib.context(dist.local)
     only = set(a.only.split(",")) if a.only else {"z3", "join", "extra", "table"}
+    if not a.full:   # a plain run: the headline's timed steps and nothing that needs a run of its own
+        only = {"z3"}
+        a.no_cpu = a.no_extra = True
     dev = torch.device("cuda", dist.local)
     N = a.points
     out = {"metric": METRIC, "unit": "points/s", "n_gpus": dist.world, "steps": a.steps, "warmup": a.warmup,
@@ -912,10 +960,13 @@ def main():
     ms = None
     if "z3" in only:
         ms = timed(dist, z3_step, a.steps, a.warmup)
-        st = _lib.BatchStatus()
-        _lib.check(lib.gm_z3_index_key(h, P(x), P(y), P(t), N, 1, 0, P(b), P(z), None, __import__("ctypes").byref(st)),
-                   "z3")
-        assert st.n_errors == 0
+        if a.dump_outputs and dist.rank == 0:
+            dump_outputs(a.dump_outputs, b, z)
+        if a.full:   # one more pass that also fills the batch status (no point may fail to key)
+            st = _lib.BatchStatus()
+            _lib.check(lib.gm_z3_index_key(h, P(x), P(y), P(t), N, 1, 0, P(b), P(z), None,
+                                           __import__("ctypes").byref(st)), "z3")
+            assert st.n_errors == 0
         if dist.rank == 0 and not a.no_cpu:   # strided sample of this run for the CPU leg
             stride = max(1, N // 4_000_000)
             z3_sample = tuple(v[::stride].cpu().numpy() for v in (x, y, t, b, z)) + (stride,)
@@ -927,11 +978,13 @@ def main():
         # this box's own streaming ceiling beside the spec peak: the HBM rate of a device-to-device copy
         # of the same 34 GB shape (HBM rates differ between boxes by up to ~15%), so the fraction can be
         # compared across captures
-        cp = box_copy_gbs(dist, x, ctx)
-        out["roofline"]["box_copy_gbs"] = round(cp, 1)
-        out["roofline"]["frac_of_box_copy"] = round(out["roofline"]["achieved"] / cp, 4)
-        out["roofline"]["box_copy_note"] = ("4 GB device-to-device copy (gm_device_copy: 16 B per lane, non-temporal, "
-                                            "the encode kernels' access shape), best of 6, read + write bytes / time")
+        if a.full:
+            cp = box_copy_gbs(dist, x, ctx)
+            out["roofline"]["box_copy_gbs"] = round(cp, 1)
+            out["roofline"]["frac_of_box_copy"] = round(out["roofline"]["achieved"] / cp, 4)
+            out["roofline"]["box_copy_note"] = ("4 GB device-to-device copy (gm_device_copy: 16 B per lane, "
+                                                "non-temporal, the encode kernels' access shape), best of 6, "
+                                                "read + write bytes / time")
     out["config"] = {"workload": "configs[1]: Z3IndexKeySpace.toIndexKey batch (BinnedTime + Z3SFC(week).index), "
                                  "%d resident points per GPU" % N,
                      "points_per_gpu": N, "period": "week", "parallelism": "point shards, no collective"}

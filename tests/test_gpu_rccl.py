@@ -126,7 +126,7 @@ def test_bench_under_torchrun_world1(gpu):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--join-steps", "1", "--points", "8000000",
+           "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--join-steps", "1", "--points", "8000000",
            "--join-points", "4000000", "--table-rows", "2000000", "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]

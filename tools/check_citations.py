@@ -1,38 +1,57 @@
-"""Checks every `File.scala:N[-M]` / `File.java:N` citation in the repo against /root/reference.
+"""Checks every `File.scala:N[-M]` / `File.java:N` citation in the repo against the reference's files.
 
 A citation is flagged when no reference file of that name (narrowed by any path prefix written
 before it) has at least M lines.  Line ranges written after a citation as `,A-B` or `, :A` are
 checked against the same file.  Run from the repo root; exits 1 when something is flagged.
-Used by tests/test_citations.py (skipped where /root/reference is absent, e.g. on the GPU box).
+
+The reference is known here by a recorded list alone, tests/golden/reference_lines.tsv: one
+`<line count>\t<path inside the reference>` row per Scala / Java file.  With a reference checkout at
+hand, `python tools/check_citations.py --index <checkout>` writes that list again.
+Used by tests/test_citations.py.
 """
 import os
 import re
 import sys
 
-REF = "/root/reference"
+HERE = os.path.dirname(os.path.abspath(__file__))
+INDEX = os.path.join(os.path.dirname(HERE), "tests", "golden", "reference_lines.tsv")
 EXTS = (".py", ".c", ".h", ".hip", ".hpp", ".md", ".sh")
 SKIP_FILES = {"SURVEY.md", "VERDICT.md", "ADVICE.md", "PAPERS.md", "SNIPPETS.md", "BASELINE.md"}
 # ambiguous basenames cited without a path in this repo
 ALIASES = {"package.scala": "zorder/sfcurve"}
 CITE = re.compile(r"((?:[\w\-.]+/|\.\.\./)*)([A-Za-z][\w]*\.(?:scala|java))((?::\d+(?:-\d+)?)(?:,\s*:?\d+(?:-\d+)?)*)")
 
-
-def ref_index():
-    idx = {}
-    for root, _, files in os.walk(REF):
-        for f in files:
-            if f.endswith((".scala", ".java")):
-                idx.setdefault(f, []).append(os.path.join(root, f))
-    return idx
-
-
 _lines = {}
 
 
+def write_index(ref, out=INDEX):
+    """Records the line count of every Scala / Java file under `ref` (paths relative to it, sorted)."""
+    rows = []
+    for root, dirs, files in os.walk(ref):
+        dirs[:] = [d for d in dirs if not d.startswith(".")]
+        for f in files:
+            if f.endswith((".scala", ".java")):
+                p = os.path.join(root, f)
+                with open(p, "rb") as fh:
+                    rows.append((os.path.relpath(p, ref).replace(os.sep, "/"), fh.read().count(b"\n") + 1))
+    with open(out, "w", encoding="utf-8") as fh:
+        for p, n in sorted(rows):
+            fh.write("%d\t%s\n" % (n, p))
+    return len(rows)
+
+
+def ref_index():
+    idx = {}
+    with open(INDEX, encoding="utf-8") as fh:
+        for row in fh:
+            n, p = row.rstrip("\n").split("\t", 1)
+            p = "/" + p
+            _lines[p] = int(n)
+            idx.setdefault(p.rsplit("/", 1)[1], []).append(p)
+    return idx
+
+
 def nlines(p):
-    if p not in _lines:
-        with open(p, "rb") as fh:
-            _lines[p] = fh.read().count(b"\n") + 1
     return _lines[p]
 
 
@@ -72,6 +91,9 @@ def check(root="."):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] == "--index":
+        print("%d files recorded in %s" % (write_index(sys.argv[2]), INDEX))
+        sys.exit(0)
     out = check(sys.argv[1] if len(sys.argv) > 1 else ".")
     for p, ln, c, why in out:
         print("%s:%d: %s (%s)" % (p, ln, c, why))

@@ -7,7 +7,7 @@
 # steps:
 #   tests[:K]        pytest -m gpu (only tests matching -k K when given)
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (stdout json + detail)
+#   bench            the bench line with every leg (bench.py --full: stdout json + detail)
 #   prof             rocprofv3 --kernel-trace --stats of the bench, then the FETCH_SIZE / WRITE_SIZE /
 #                    FP64 passes (one counter group per run) -> make_traffic.py input
 #   kstats:LEG       rocprofv3 --kernel-trace --stats of one leg (summary via tools/kstats.py)
@@ -25,12 +25,12 @@ out=gpurun_out/$tag
 
 leg_args() {   # the bench arguments of one leg
   case $1 in
-    join) echo "--only join --no-cpu --no-gather --steps 1 --warmup 0 --join-steps 3" ;;
-    ranges) echo "--only extra --no-cpu --no-gather --steps 2 --warmup 1" ;;
-    table) echo "--only z3,table --no-cpu --steps 2 --warmup 1" ;;   # the table's keys come from the z3 leg
-    z3) echo "--only z3 --no-cpu --steps 10 --warmup 2" ;;
-    extra) echo "--only extra --no-cpu --steps 6 --warmup 1" ;;
-    *) echo "--no-cpu" ;;
+    join) echo "--full --only join --no-cpu --no-gather --steps 1 --warmup 0 --join-steps 3" ;;
+    ranges) echo "--full --only extra --no-cpu --no-gather --steps 2 --warmup 1" ;;
+    table) echo "--full --only z3,table --no-cpu --steps 2 --warmup 1" ;;   # the table's keys come from the z3 leg
+    z3) echo "--full --only z3 --no-cpu --steps 10 --warmup 2" ;;
+    extra) echo "--full --only extra --no-cpu --steps 6 --warmup 1" ;;
+    *) echo "--full --no-cpu" ;;
   esac
 }
 
@@ -46,26 +46,26 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > ${out}_smoke.log 2>&1 ;;
     n2)   # the N > 1 paths with two ranks on the box's one GPU and gloo collectives (reduced sizes)
       GM_BENCH_DEVICE=0 GM_BENCH_BACKEND=gloo timeout -k 10 900 python -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 3 --warmup 1 \
+        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --steps 3 --warmup 1 \
         --join-steps 2 --points 250000000 --join-points 250000000 --table-rows 100000000 \
         > ${out}_n2.json 2> ${out}_n2.err
       cp gpurun_out/bench_detail_n2.json ${out}_n2_detail.json ;;
     bench)
-      timeout -k 10 600 python -u bench.py > ${out}_bench.json 2> ${out}_bench.err
+      timeout -k 10 600 python -u bench.py --full > ${out}_bench.json 2> ${out}_bench.err
       cp gpurun_out/bench_detail_n1.json ${out}_bench_detail.json ;;
     prof)
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d ${out}_prof -o run -- \
-        python3 bench.py --steps 10 --join-steps 3 --no-cpu > ${out}_prof_bench.json 2> ${out}_prof.err
+        python3 bench.py --full --steps 10 --join-steps 3 --no-cpu > ${out}_prof_bench.json 2> ${out}_prof.err
       i=0
       rq="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum"
       for g in FETCH_SIZE WRITE_SIZE "$rq"; do
         timeout -s KILL 200 rocprofv3 --kernel-trace --output-format csv --pmc $g -d ${out}_pmc/p$i -o run -- \
-          python3 bench.py --only z3,extra,table --no-cpu --steps 2 --warmup 1 > ${out}_pmc$i.log 2>&1
+          python3 bench.py --full --only z3,extra,table --no-cpu --steps 2 --warmup 1 > ${out}_pmc$i.log 2>&1
         i=$((i+1))
       done
       for g in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU_FLOPS_FP64 "$rq"; do
         timeout -s KILL 200 rocprofv3 --kernel-trace --output-format csv --pmc $g -d ${out}_pmc/p$i -o run -- \
-          python3 bench.py --only join --no-cpu --steps 1 --warmup 0 --join-steps 1 > ${out}_pmc$i.log 2>&1
+          python3 bench.py --full --only join --no-cpu --steps 1 --warmup 0 --join-steps 1 > ${out}_pmc$i.log 2>&1
         i=$((i+1))
       done ;;
     tpmc)   # the traffic-calibration probe: its own timing, then one counter group per rocprofv3 pass
