@@ -640,25 +640,22 @@ namespace gm {
 int alloc_scan(gm_ctx* ctx, int64_t n, uint64_t* user_mask, size_t desc_words, ScanBufs& b) {
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
   const int64_t nwords = nblocks * (FROWS / 64);
-  const size_t a_mask = user_mask ? 0 : (size_t)nwords * 8;
-  const size_t a_cnt = ((size_t)nblocks * 4 + 4 + 15) & ~(size_t)15;
-  const size_t a_off = ((size_t)(nblocks + 1) * 8 + 15) & ~(size_t)15;
-  const size_t a_part = ((size_t)(nblocks / SCAN_CHUNK + 2) * 8 + 15) & ~(size_t)15;
-  const size_t a_desc = (desc_words * 4 + 15) & ~(size_t)15;
-  void* base = nullptr;
-  int rc = ctx_workspace(ctx, WS_SCAN, a_mask + a_cnt + a_off + a_part + a_desc + 16, &base);
+  Carve c{16};
+  const size_t o_mask = c.take(user_mask ? 0 : (size_t)nwords * 8);   // whole 512-B blocks: no rounding
+  const size_t o_cnt = c.take((size_t)nblocks * 4 + 4);
+  const size_t o_off = c.take((size_t)(nblocks + 1) * 8);
+  const size_t o_part = c.take((size_t)(nblocks / SCAN_CHUNK + 2) * 8);
+  const size_t o_desc = c.take(desc_words * 4);
+  char* base = nullptr;
+  int rc = ctx_workspace(ctx, WS_SCAN, c.total + 16, (void**)&base);
   if (rc) return rc;
-  char* p = (char*)base;
-  b.mask = user_mask ? user_mask : (uint64_t*)p;
-  p += a_mask;
-  b.counts = (int32_t*)p; p += a_cnt;
-  b.offsets = (int64_t*)p; p += a_off;
-  b.partials = (int64_t*)p; p += a_part;
-  b.desc = desc_words ? (int32_t*)p : nullptr;
+  b.mask = user_mask ? user_mask : (uint64_t*)(base + o_mask);
+  b.counts = (int32_t*)(base + o_cnt);
+  b.offsets = (int64_t*)(base + o_off);
+  b.partials = (int64_t*)(base + o_part);
+  b.desc = desc_words ? (int32_t*)(base + o_desc) : nullptr;
   return GM_OK;
 }
-
-void free_scan(gm_ctx*, uint64_t*, ScanBufs&) {}   // workspace memory stays with the context
 
 // passes B and C + count readback
 int finish_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_cap, int64_t* n_match) {
@@ -735,7 +732,6 @@ int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len
                        fwords, d_desc + fwords, n_bin_ranges, b.mask, b.counts);
   GM_CHECK_LAUNCH();
   rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  free_scan(ctx, mask, b);
   if (rc) return rc;
   if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
   return GM_OK;
@@ -778,7 +774,6 @@ int gm_z2filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len
                        d_xy, nxy, b.mask, b.counts);
   GM_CHECK_LAUNCH();
   rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  free_scan(ctx, mask, b);
   if (rc) return rc;
   if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
   return GM_OK;
@@ -874,7 +869,6 @@ int gm_strict_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t*
                        bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask, b.counts);
   GM_CHECK_LAUNCH();
   rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  free_scan(ctx, mask, b);
   if (rc) return rc;
   if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
   return GM_OK;
@@ -944,13 +938,14 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
     return GM_OK;
   }
   hipStream_t s = ctx->stream;
+  DevTemps tmp(s);
   DevRange* d_rg = nullptr;
   int64_t *start = nullptr, *coff = nullptr;
-  GM_HIP(hipMallocAsync((void**)&d_rg, (size_t)nr * sizeof(DevRange), s));
-  GM_HIP(hipMallocAsync((void**)&start, (size_t)nr * 8, s));
-  GM_HIP(hipMallocAsync((void**)&coff, (size_t)(nr + 1) * 8, s));
-  int crc = copy_h2d(ctx, d_rg, dr.data(), (size_t)nr * sizeof(DevRange));
-  if (crc) return crc;
+  int rc = tmp.alloc_async((size_t)nr * sizeof(DevRange), &d_rg);
+  if (!rc) rc = tmp.alloc_async((size_t)nr * 8, &start);
+  if (!rc) rc = tmp.alloc_async((size_t)(nr + 1) * 8, &coff);
+  if (!rc) rc = copy_h2d(ctx, d_rg, dr.data(), (size_t)nr * sizeof(DevRange));
+  if (rc) return rc;
   hipLaunchKernelGGL(k_range_bounds, dim3((unsigned)((nr + FTPB - 1) / FTPB)), dim3(FTPB), 0, s, shard,
                      (const uint16_t*)bin, (const uint64_t*)z, n, d_rg, nr, start, coff);
   hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, s, coff, nr);
@@ -959,7 +954,6 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
   GM_HIP(hipStreamSynchronize(s));  // dr is pageable; the candidate count sizes the pass below
   const int64_t total = ctx->h_pinned[0];
   if (n_scanned) *n_scanned = total;
-  int rc = GM_OK;
   int64_t nm = 0;
   if (total > 0) {
     // device descriptor: [query boxes f64 x 4 nbox][row-filter words]
@@ -969,39 +963,34 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
     if (!desc.empty()) memcpy(buf.data() + box_words, desc.data(), desc.size() * 4);
     ScanBufs b;
     rc = alloc_scan(ctx, total, nullptr, buf.size() + 4, b);
-    if (!rc) {
-      if (!buf.empty()) {
-        GM_HIP(hipMemcpyAsync(b.desc, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, s));
-        GM_HIP(hipStreamSynchronize(s));
-      }
-      FullFilter ff{f->xmin, f->ymin, f->xmax, f->ymax, f->t_ms, env ? (const double*)b.desc : nullptr, f->n_boxes,
-                    f->t_lo, f->t_hi, perm};
-      const int32_t* d_desc = b.desc + box_words;
-      const int64_t nblocks = (total + FROWS - 1) / FROWS;
-      void (*kern)(const uint16_t*, const uint64_t*, const int64_t*, const int64_t*, int64_t, int64_t, const int32_t*,
-                   int, FullFilter, uint64_t*, int32_t*) = nullptr;
+    if (rc) return rc;
+    if (!buf.empty()) {
+      GM_HIP(hipMemcpyAsync(b.desc, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, s));
+      GM_HIP(hipStreamSynchronize(s));
+    }
+    FullFilter ff{f->xmin, f->ymin, f->xmax, f->ymax, f->t_ms, env ? (const double*)b.desc : nullptr, f->n_boxes,
+                  f->t_lo, f->t_hi, perm};
+    const int32_t* d_desc = b.desc + box_words;
+    const int64_t nblocks = (total + FROWS - 1) / FROWS;
+    void (*kern)(const uint16_t*, const uint64_t*, const int64_t*, const int64_t*, int64_t, int64_t, const int32_t*,
+                 int, FullFilter, uint64_t*, int32_t*) = nullptr;
 #define GM_RANGE_MASK(R)                                                                   \
   (env ? (dur ? k_range_mask<R, true, true> : k_range_mask<R, true, false>)               \
        : (dur ? k_range_mask<R, false, true> : k_range_mask<R, false, false>))
-      kern = rf == RF_Z3 ? GM_RANGE_MASK(RF_Z3) : rf == RF_Z2 ? GM_RANGE_MASK(RF_Z2) : GM_RANGE_MASK(RF_NONE);
+    kern = rf == RF_Z3 ? GM_RANGE_MASK(RF_Z3) : rf == RF_Z2 ? GM_RANGE_MASK(RF_Z2) : GM_RANGE_MASK(RF_NONE);
 #undef GM_RANGE_MASK
-      hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(FTPB), 0, s, (const uint16_t*)bin, (const uint64_t*)z, coff,
-                         start, nr, total, d_desc, nxy, ff, b.mask, b.counts);
-      if (hipGetLastError() != hipSuccess) rc = hip_fail(hipErrorLaunchFailure, "k_range_mask");
-      if (!rc) rc = finish_scan(ctx, total, b, ids, ids_cap, &nm);
-      if (!rc && ids && nm > 0) {
-        const int64_t m = std::min(nm, ids_cap);
-        hipLaunchKernelGGL(k_cand_to_row, dim3((unsigned)std::min<int64_t>(4096, (m + FTPB - 1) / FTPB)), dim3(FTPB), 0,
-                           s, ids, m, coff, start, nr, perm);
-        if (hipGetLastError() != hipSuccess) rc = hip_fail(hipErrorLaunchFailure, "k_cand_to_row");
-      }
-      free_scan(ctx, nullptr, b);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(FTPB), 0, s, (const uint16_t*)bin, (const uint64_t*)z, coff,
+                       start, nr, total, d_desc, nxy, ff, b.mask, b.counts);
+    GM_CHECK_LAUNCH();
+    rc = finish_scan(ctx, total, b, ids, ids_cap, &nm);
+    if (rc) return rc;
+    if (ids && nm > 0) {
+      const int64_t m = std::min(nm, ids_cap);
+      hipLaunchKernelGGL(k_cand_to_row, dim3((unsigned)std::min<int64_t>(4096, (m + FTPB - 1) / FTPB)), dim3(FTPB), 0,
+                         s, ids, m, coff, start, nr, perm);
+      GM_CHECK_LAUNCH();
     }
   }
-  (void)hipFreeAsync(d_rg, s);
-  (void)hipFreeAsync(start, s);
-  (void)hipFreeAsync(coff, s);
-  if (rc) return rc;
   if (n_match) *n_match = nm;
   if (ids && nm > ids_cap) return GM_E_CAPACITY;
   return GM_OK;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/geomesa_hip.h"
 #include "gm_device.hpp"
@@ -68,6 +69,68 @@ int copy_h2d(gm_ctx* ctx, void* dev, const void* host, size_t bytes);
 // (0.7-6 s stalls between launches).  slot: 0 = range batches, 1 = sort, 2 = scans, 3 = join.
 enum : int { WS_RANGES = 0, WS_SORT = 1, WS_SCAN = 2, WS_JOIN = 3 };
 int ctx_workspace(gm_ctx* ctx, int slot, size_t bytes, void** p);
+
+// Region offsets of one workspace request: take() returns the region's offset and advances `total` by
+// its size rounded up to `align`, so the sum asked of ctx_workspace and the pointers formed from its
+// base come from the same calls.
+struct Carve {
+  size_t align, total = 0;
+  constexpr size_t take(size_t bytes) {
+    const size_t at = total;
+    total += (bytes + align - 1) / align * align;
+    return at;
+  }
+};
+namespace carve_check {
+constexpr Carve a16{16}, a256{256};
+constexpr size_t offs(Carve c, size_t x, size_t y, size_t z, int k) {
+  const size_t o[4] = {c.take(x), c.take(y), c.take(z), c.total};
+  return o[k];
+}
+static_assert(offs(a16, 1, 16, 17, 0) == 0 && offs(a16, 1, 16, 17, 1) == 16 && offs(a16, 1, 16, 17, 2) == 32 &&
+                  offs(a16, 1, 16, 17, 3) == 64, "sizes round up to the alignment");
+static_assert(offs(a256, 8, 257, 256, 1) == 256 && offs(a256, 8, 257, 256, 2) == 768 &&
+                  offs(a256, 8, 257, 256, 3) == 1024, "256-B regions");
+static_assert(offs(a16, 0, 8, 0, 1) == 0 && offs(a16, 0, 8, 0, 2) == 16 && offs(a16, 0, 8, 0, 3) == 16,
+              "an empty region takes no bytes");
+static_assert(offs(a16, 3, 5, 7, 3) % 16 == 0 && offs(a256, 3, 5, 7, 3) % 256 == 0, "totals stay aligned");
+}  // namespace carve_check
+
+// Owner of one call's device temporaries: every buffer it hands out is freed when it goes out of
+// scope, so no return path (the ones inside GM_HIP / GM_CHECK_LAUNCH included) leaks.  alloc buffers
+// leave through hipFree, which waits for the device; alloc_async buffers come from the stream's pool
+// and leave stream-ordered.  Either is safe after work enqueued on the stream.  Buffers that outlive
+// the call (index arrays) are not allocated here.
+class DevTemps {
+ public:
+  explicit DevTemps(hipStream_t s) : s_(s) {}
+  DevTemps(const DevTemps&) = delete;
+  DevTemps& operator=(const DevTemps&) = delete;
+  ~DevTemps() {
+    for (const Buf& b : bufs_) (void)(b.async ? hipFreeAsync(b.p, s_) : hipFree(b.p));
+  }
+  template <class T>
+  int alloc(size_t bytes, T** p) {
+    GM_HIP(hipMalloc((void**)p, bytes < 16 ? 16 : bytes));
+    bufs_.push_back(Buf{*p, false});
+    return GM_OK;
+  }
+  template <class T>
+  int alloc_async(size_t bytes, T** p) {
+    GM_HIP(hipMallocAsync((void**)p, bytes < 16 ? 16 : bytes, s_));
+    bufs_.push_back(Buf{*p, true});
+    return GM_OK;
+  }
+
+ private:
+  struct Buf {
+    void* p;
+    bool async;
+  };
+  hipStream_t s_;
+  std::vector<Buf> bufs_;
+};
+
 bool host_pinned(const void* p);
 bool device_memory(const void* p);   // device (hipMalloc) memory, as opposed to host memory
 int ctx_copy_stream(gm_ctx* ctx);   // creates copy_stream and its events on first use

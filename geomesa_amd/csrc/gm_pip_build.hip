@@ -958,22 +958,21 @@ int make_shortcut(gm_pip_index* ix) {
   }
   if (ncell == 0) return GM_OK;
   const bool lines_ok = ix->arr_bytes[5] / 128 < (int64_t)SC_LINE;   // compact indices below the LINE bit
+  DevTemps tmp(s);   // scratch: line flags, their scan, the scan's partials
   void *fl = nullptr, *sl = nullptr, *part = nullptr;
-  auto cleanup = [&]() { (void)hipFree(fl); (void)hipFree(sl); (void)hipFree(part); };
-  if (hipMalloc(&fl, (size_t)ncell * 4) != hipSuccess || hipMalloc(&sl, (size_t)(ncell + 1) * 8) != hipSuccess ||
-      hipMalloc(&part, (size_t)scan_partials_len(ncell) * 8) != hipSuccess) {
-    cleanup();
-    return hip_fail(hipErrorOutOfMemory, "gm_pip_index shortcut");
-  }
+  int rc = tmp.alloc((size_t)ncell * 4, &fl);
+  if (!rc) rc = tmp.alloc((size_t)(ncell + 1) * 8, &sl);
+  if (!rc) rc = tmp.alloc((size_t)scan_partials_len(ncell) * 8, &part);
+  if (rc) return rc;
   const unsigned g = (unsigned)std::min<int64_t>(65536, (ncell + 255) / 256);
   hipLaunchKernelGGL(k_build_shortcut<false>, dim3(g), dim3(256), 0, s, ix->dev, ncell, (uint32_t*)p, (int32_t*)fl,
                      nullptr, nullptr);
   launch_excl_scan(s, (const int32_t*)fl, ncell, (int64_t*)sl, (int64_t*)part, (int64_t*)sl + ncell);
   int64_t nl = 0;
-  int rc = copy_d2h(ix->ctx, &nl, (int64_t*)sl + ncell, 8);
+  rc = copy_d2h(ix->ctx, &nl, (int64_t*)sl + ncell, 8);
   if (!rc && nl > 0 && lines_ok && nl < (int64_t)SC_LINE) {
     void* e = nullptr;
-    if (hipMalloc(&e, (size_t)nl * 2 * sizeof(uint4)) != hipSuccess) { cleanup(); return hip_fail(hipErrorOutOfMemory, "gm_pip_index lines"); }
+    if (hipMalloc(&e, (size_t)nl * 2 * sizeof(uint4)) != hipSuccess) return hip_fail(hipErrorOutOfMemory, "gm_pip_index lines");
     ix->allocs.push_back(e);
     ix->dev.line_ent = (const uint4*)e;
     ix->n_lines = nl;
@@ -1010,10 +1009,9 @@ int make_shortcut(gm_pip_index* ix) {
     };
     rc = bitmap(CM_WORDS_MAX, &ix->dev.cm, &ix->dev.cm_shift, &ix->dev.cm_shift_y, &ix->dev.cm_w, &ix->dev.cm_words);
     if (!rc) rc = bitmap(RM_WORDS_MAX, &ix->dev.rm, &ix->dev.rm_shift, &ix->dev.rm_shift_y, &ix->dev.rm_w, &ix->dev.rm_words);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
   }
   if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = hip_fail(hipErrorLaunchFailure, "k_build_shortcut");
-  cleanup();
   if (!rc && getenv("GM_PIP_DEBUG")) {   // coverage (diagnostic copies)
     std::vector<uint32_t> cw((size_t)ncell), sc((size_t)ncell);
     GM_HIP(hipMemcpy(cw.data(), ix->dev.cell_word, (size_t)ncell * 4, hipMemcpyDeviceToHost));
@@ -1143,15 +1141,9 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   // polygon's edge count per row task): those sets are left to the host build
   if (band_total > ((int64_t)1 << 27)) return 1;
   const int64_t ncell = (int64_t)gx * gy;
-  std::vector<void*> tmp;
-  auto dalloc = [&](size_t bytes, void** p) -> int {
-    GM_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
-    tmp.push_back(*p);
-    return GM_OK;
-  };
-  auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); tmp.clear(); };
+  DevTemps tmp(s);   // every scratch buffer of this build
   auto up = [&](const void* h, size_t bytes, void** d) -> int {
-    int rc = dalloc(bytes, d);
+    int rc = tmp.alloc(bytes, d);
     if (!rc && bytes) rc = copy_h2d(ctx, *d, h, bytes);
     return rc;
   };
@@ -1169,21 +1161,21 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   if (!rc) rc = up(task_slot.data(), (size_t)(ntask + 1) * 8, &d_ts);
   if (!rc) rc = up(band_off.data(), (size_t)ntask * 8, &d_bo);
   void *d_bseg = nullptr, *d_bring = nullptr, *d_bmnx = nullptr, *d_bmxx = nullptr, *d_bmny = nullptr, *d_bmxy = nullptr;
-  if (!rc) rc = dalloc((size_t)band_total * 4, &d_bseg);
-  if (!rc) rc = dalloc((size_t)band_total * 4, &d_bring);
-  if (!rc) rc = dalloc((size_t)band_total * 8, &d_bmnx);
-  if (!rc) rc = dalloc((size_t)band_total * 8, &d_bmxx);
-  if (!rc) rc = dalloc((size_t)band_total * 8, &d_bmny);
-  if (!rc) rc = dalloc((size_t)band_total * 8, &d_bmxy);
+  if (!rc) rc = tmp.alloc((size_t)band_total * 4, &d_bseg);
+  if (!rc) rc = tmp.alloc((size_t)band_total * 4, &d_bring);
+  if (!rc) rc = tmp.alloc((size_t)band_total * 8, &d_bmnx);
+  if (!rc) rc = tmp.alloc((size_t)band_total * 8, &d_bmxx);
+  if (!rc) rc = tmp.alloc((size_t)band_total * 8, &d_bmny);
+  if (!rc) rc = tmp.alloc((size_t)band_total * 8, &d_bmxy);
   void *d_gw, *d_cl, *d_goff, *d_coff, *d_part, *d_stat;
   const int64_t np = scan_partials_len(nslot);
-  if (!rc) rc = dalloc((size_t)nslot * 4, &d_gw);
-  if (!rc) rc = dalloc((size_t)nslot * 4, &d_cl);
-  if (!rc) rc = dalloc((size_t)(nslot + 1) * 8, &d_goff);
-  if (!rc) rc = dalloc((size_t)(nslot + 1) * 8, &d_coff);
-  if (!rc) rc = dalloc((size_t)std::max(np, scan_partials_len(ncell)) * 8, &d_part);
-  if (!rc) rc = dalloc(8 * 8, &d_stat);
-  if (rc) { cleanup(); return rc; }
+  if (!rc) rc = tmp.alloc((size_t)nslot * 4, &d_gw);
+  if (!rc) rc = tmp.alloc((size_t)nslot * 4, &d_cl);
+  if (!rc) rc = tmp.alloc((size_t)(nslot + 1) * 8, &d_goff);
+  if (!rc) rc = tmp.alloc((size_t)(nslot + 1) * 8, &d_coff);
+  if (!rc) rc = tmp.alloc((size_t)std::max(np, scan_partials_len(ncell)) * 8, &d_part);
+  if (!rc) rc = tmp.alloc(8 * 8, &d_stat);
+  if (rc) return rc;
   GM_HIP(hipMemsetAsync(d_stat, 0, 64, s));
   a.poly_part_off = (const int32_t*)d_ppo; a.part_ring_off = (const int32_t*)d_pro;
   a.ring_vert_off = (const int32_t*)d_rvo; a.vx = (const double*)d_vx; a.vy = (const double*)d_vy;
@@ -1208,9 +1200,8 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   rc = copy_d2h(ctx, &tot_words, (int64_t*)d_goff + nslot, 8);
   if (!rc) rc = copy_d2h(ctx, &tot_lines, (int64_t*)d_coff + nslot, 8);
   if (!rc) rc = copy_d2h(ctx, st, d_stat, sizeof st);
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   if (tot_words / 2 >= (int64_t)BLOB_COMPACT || tot_lines >= (int64_t)BLOB_COMPACT) {
-    cleanup();
     gm::set_error("gm_pip_index_create: boundary blobs too large (lower cells_per_poly)");
     return GM_E_CAPACITY;
   }
@@ -1227,13 +1218,13 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   rc = own(7, (size_t)blob_words * 8, &d_blob);
   if (!rc) rc = own(5, (size_t)cmp_words * 8, &d_cmp);
   if (!rc) rc = own(3, (size_t)ncell * 4, &d_cw);
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   GM_HIP(hipMemsetAsync(d_blob, 0, (size_t)blob_words * 8, s));
   GM_HIP(hipMemsetAsync(d_cmp, 0, (size_t)cmp_words * 8, s));
   void *d_ew, *d_ec;
-  rc = dalloc((size_t)nslot * 4, &d_ew);
-  if (!rc) rc = dalloc((size_t)nslot * 4, &d_ec);
-  if (rc) { cleanup(); return rc; }
+  rc = tmp.alloc((size_t)nslot * 4, &d_ew);
+  if (!rc) rc = tmp.alloc((size_t)nslot * 4, &d_ec);
+  if (rc) return rc;
   a.write = 1;
   a.gen_off = (const int64_t*)d_goff; a.cmp_off = (const int64_t*)d_coff;
   a.ent_word = (uint32_t*)d_ew; a.ent_cell = (int32_t*)d_ec;
@@ -1242,15 +1233,15 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   GM_CHECK_LAUNCH();
   // entries per cell -> buckets -> cell words and lists
   void *d_pc, *d_bc, *d_cs, *d_fill, *d_sp, *d_ll, *d_lo, *d_max;
-  rc = dalloc((size_t)ncell * 4, &d_pc);
-  if (!rc) rc = dalloc((size_t)ncell * 4, &d_bc);
-  if (!rc) rc = dalloc((size_t)(ncell + 1) * 8, &d_cs);
-  if (!rc) rc = dalloc((size_t)ncell * 4, &d_fill);
-  if (!rc) rc = dalloc((size_t)nslot * 4, &d_sp);
-  if (!rc) rc = dalloc((size_t)ncell * 4, &d_ll);
-  if (!rc) rc = dalloc((size_t)(ncell + 1) * 8, &d_lo);
-  if (!rc) rc = dalloc(16, &d_max);
-  if (rc) { cleanup(); return rc; }
+  rc = tmp.alloc((size_t)ncell * 4, &d_pc);
+  if (!rc) rc = tmp.alloc((size_t)ncell * 4, &d_bc);
+  if (!rc) rc = tmp.alloc((size_t)(ncell + 1) * 8, &d_cs);
+  if (!rc) rc = tmp.alloc((size_t)ncell * 4, &d_fill);
+  if (!rc) rc = tmp.alloc((size_t)nslot * 4, &d_sp);
+  if (!rc) rc = tmp.alloc((size_t)ncell * 4, &d_ll);
+  if (!rc) rc = tmp.alloc((size_t)(ncell + 1) * 8, &d_lo);
+  if (!rc) rc = tmp.alloc(16, &d_max);
+  if (rc) return rc;
   GM_HIP(hipMemsetAsync(d_pc, 0, (size_t)ncell * 4, s));
   GM_HIP(hipMemsetAsync(d_bc, 0, (size_t)ncell * 4, s));
   GM_HIP(hipMemsetAsync(d_fill, 0, (size_t)ncell * 4, s));
@@ -1264,10 +1255,10 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   GM_CHECK_LAUNCH();
   int64_t n_ent = 0;
   rc = copy_d2h(ctx, &n_ent, (int64_t*)d_cs + ncell, 8);
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   void* d_bucket;
-  rc = dalloc((size_t)std::max<int64_t>(n_ent, 1) * 8, &d_bucket);
-  if (rc) { cleanup(); return rc; }
+  rc = tmp.alloc((size_t)std::max<int64_t>(n_ent, 1) * 8, &d_bucket);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_build_cell_scatter, dim3(g1), dim3(256), 0, s, (const uint32_t*)d_ew, (const int32_t*)d_ec, nslot,
                      (const int64_t*)d_cs, (int32_t*)d_fill, (uint32_t*)d_bucket, (const int32_t*)d_sp);
   hipLaunchKernelGGL(k_build_list_len, dim3(g1), dim3(256), 0, s, (const int32_t*)d_pc, ncell, (int32_t*)d_ll);
@@ -1275,22 +1266,21 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   GM_CHECK_LAUNCH();
   int64_t n_list = 0;
   rc = copy_d2h(ctx, &n_list, (int64_t*)d_lo + ncell, 8);
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   if (n_list / 4 + 1 >= ((int64_t)1 << 26)) {
-    cleanup();
     gm::set_error("gm_pip_index_create: cell lists too large");
     return GM_E_CAPACITY;
   }
   const int64_t list_slots = std::max<int64_t>(n_list, 4);
   rc = own(6, (size_t)list_slots * 4, &d_list);
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   GM_HIP(hipMemsetAsync(d_list, 0, (size_t)list_slots * 4, s));
   hipLaunchKernelGGL(k_build_cells, dim3(g1), dim3(256), 0, s, (const int32_t*)d_pc, (const int64_t*)d_cs,
                      (uint32_t*)d_bucket, (const int64_t*)d_lo, ncell, (uint32_t*)d_cw, (uint32_t*)d_list);
   GM_CHECK_LAUNCH();
   const int gxc = (gx + (1 << CF_LOG) - 1) >> CF_LOG, gyc = (gy + (1 << CF_LOG) - 1) >> CF_LOG;
   rc = own(4, (size_t)gxc * gyc * 4, &d_coarse);
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   hipLaunchKernelGGL(k_build_coarse, dim3((unsigned)std::min<int64_t>(65536, ((int64_t)gxc * gyc + 255) / 256)),
                      dim3(256), 0, s, (const uint32_t*)d_cw, gx, gy, gxc, gyc, (uint32_t*)d_coarse);
   hipLaunchKernelGGL(k_build_max, dim3(g1), dim3(256), 0, s, (const int32_t*)d_pc, ncell, (int*)d_max);
@@ -1298,7 +1288,6 @@ int build_cells_device(gm_ctx* ctx, gm_pip_index* ix, const gm_polyset* ps, cons
   GM_CHECK_LAUNCH();
   int mx[2] = {0, 0};
   rc = copy_d2h(ctx, mx, d_max, 8);
-  cleanup();
   if (rc) return rc;
   ix->dev.cell_word = (const uint32_t*)d_cw;
   ix->dev.coarse_word = (const uint32_t*)d_coarse;

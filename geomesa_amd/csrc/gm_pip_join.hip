@@ -577,18 +577,17 @@ static int join_staged(gm_ctx* ctx, const double* px, const double* py, ArrowPts
   if (write) {   // context workspace: overflow ids | overflow polygons | wave descriptors | plan
     // reservations run at most one partial slab per launched wave past the pair count, so positions
     // in [cap, cap + wmax * SLAB) hold every pair below n_pairs when n_pairs <= cap
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const int64_t ocap = wmax * SLAB;
-    const size_t a_id = al((size_t)ocap * 8), a_pl = al((size_t)ocap * 4), a_d = al((size_t)wmax * sizeof(longlong2));
-    void* base = nullptr;
-    int rc = ctx_workspace(ctx, WS_JOIN, a_id + a_pl + a_d + sizeof(PairPlan), &base);
+    Carve c{256};
+    const size_t o_id = c.take((size_t)ocap * 8), o_pl = c.take((size_t)ocap * 4), o_d = c.take((size_t)wmax * sizeof(longlong2));
+    char* base = nullptr;
+    int rc = ctx_workspace(ctx, WS_JOIN, c.total + sizeof(PairPlan), (void**)&base);
     if (rc) return rc;
-    char* q = (char*)base;
-    po.opt = (int64_t*)q; q += a_id;
-    po.opl = (int32_t*)q; q += a_pl;
-    po.desc = (longlong2*)q; q += a_d;
+    po.opt = (int64_t*)(base + o_id);
+    po.opl = (int32_t*)(base + o_pl);
+    po.desc = (longlong2*)(base + o_d);
     po.ocap = ocap;
-    plan = (PairPlan*)q;
+    plan = (PairPlan*)(base + c.total);
   }
   for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
     const int64_t m = std::min(CHUNK, n - c0);

@@ -230,7 +230,6 @@ int gm_query_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t* 
   }
   GM_CHECK_LAUNCH();
   rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  free_scan(ctx, mask, b);
   if (rc) return rc;
   if (spatial_op != GM_SPATIAL_NONE && (rc = take_fault(ctx, "gm_query_scan"))) return rc;
   if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;

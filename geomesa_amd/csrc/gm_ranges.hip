@@ -905,10 +905,11 @@ using namespace gm;
 
 namespace {
 
+// a stream-ordered input copy of one entry point, freed by `tmp` on every return path
 template <class T>
-int to_dev(gm_ctx* ctx, const T* h, size_t n, T** d) {
-  GM_HIP(hipMallocAsync((void**)d, std::max<size_t>(n * sizeof(T), 16), ctx->stream));
-  return copy_h2d(ctx, *d, h, n * sizeof(T));
+int to_dev(gm_ctx* ctx, DevTemps& tmp, const T* h, size_t n, T** d) {
+  const int rc = tmp.alloc_async(n * sizeof(T), d);
+  return rc ? rc : copy_h2d(ctx, *d, h, n * sizeof(T));
 }
 
 // Shared driver.  Phase 1 runs every query with small workspaces (frontier / range lists of P1CAP,
@@ -926,7 +927,6 @@ int run_batch(gm_ctx* ctx, int64_t q_base, int64_t nq, int64_t fcap, int64_t rca
               int64_t* out_off, int64_t cap, int64_t* needed, int32_t* query_status, FinishFn finish) {
   hipStream_t s = ctx->stream;
   rcap = next_pow2(std::max<int64_t>(rcap, 16));
-  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
   size_t free_b = 0, total_b = 0;
   int64_t budget = (int64_t)2 << 30;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
@@ -940,29 +940,17 @@ int run_batch(gm_ctx* ctx, int64_t q_base, int64_t nq, int64_t fcap, int64_t rca
   std::vector<int32_t> stats((size_t)nq);
   for (int attempt = 0;; ++attempt) {
     // batch arrays (scan workspace): buffer | start | offsets | count | status | qmap | scan partials | total
-    gm_range* dbuf;
-    int64_t *dstart, *doff, *dparts;
-    int32_t *dcount, *dstatus, *dqmap;
-    unsigned long long* dtotal;
-    {
-      const size_t sz[8] = {al((size_t)dcap * sizeof(gm_range)), al((size_t)nq * 8), al((size_t)(nq + 1) * 8),
-                            al((size_t)nq * 4), al((size_t)nq * 4), al((size_t)nq * 4),
-                            al((size_t)scan_partials_len(nq) * 8), 16};
-      size_t tot = 0;
-      for (size_t v : sz) tot += v;
-      void* base = nullptr;
-      int rc = ctx_workspace(ctx, WS_SCAN, tot, &base);
-      if (rc) return rc;
-      char* p = (char*)base;
-      dbuf = (gm_range*)p; p += sz[0];
-      dstart = (int64_t*)p; p += sz[1];
-      doff = (int64_t*)p; p += sz[2];
-      dcount = (int32_t*)p; p += sz[3];
-      dstatus = (int32_t*)p; p += sz[4];
-      dqmap = (int32_t*)p; p += sz[5];
-      dparts = (int64_t*)p; p += sz[6];
-      dtotal = (unsigned long long*)p;
-    }
+    Carve c{16};
+    const size_t o_buf = c.take((size_t)dcap * sizeof(gm_range)), o_start = c.take((size_t)nq * 8),
+                 o_off = c.take((size_t)(nq + 1) * 8), o_count = c.take((size_t)nq * 4), o_status = c.take((size_t)nq * 4),
+                 o_qmap = c.take((size_t)nq * 4), o_parts = c.take((size_t)scan_partials_len(nq) * 8), o_total = c.take(16);
+    char* wb = nullptr;
+    int wrc = ctx_workspace(ctx, WS_SCAN, c.total, (void**)&wb);
+    if (wrc) return wrc;
+    gm_range* dbuf = (gm_range*)(wb + o_buf);
+    int64_t *dstart = (int64_t*)(wb + o_start), *doff = (int64_t*)(wb + o_off), *dparts = (int64_t*)(wb + o_parts);
+    int32_t *dcount = (int32_t*)(wb + o_count), *dstatus = (int32_t*)(wb + o_status), *dqmap = (int32_t*)(wb + o_qmap);
+    unsigned long long* dtotal = (unsigned long long*)(wb + o_total);
     GM_HIP(hipMemsetAsync(dtotal, 0, 8, s));
     // one pass over a query list with caps (fc, rc); qmap null = queries [q_base, q_base + count).  The
     // launcher's workspace is per_q(fc, rc) bytes per query, chunked by the memory budget
@@ -1136,17 +1124,6 @@ inline int64_t z_caps(int max_ranges, int D, int64_t cap_hint) {
   return std::max<int64_t>(cap_hint, 1 << 16);
 }
 
-// frees the stream-ordered input copies of one entry point on every return path
-struct StreamFrees {
-  hipStream_t s;
-  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-  explicit StreamFrees(hipStream_t st) : s(st) {}
-  ~StreamFrees() {
-    for (void* q : p)
-      if (q) (void)hipFreeAsync(q, s);
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -1163,12 +1140,11 @@ int gm_z3_ranges(gm_ctx* ctx, int64_t nq, const int32_t* box_off, const double* 
   int32_t *dbo = nullptr, *dto = nullptr;
   double* dxy = nullptr;
   int64_t* dt = nullptr;
-  StreamFrees fr(s);
-  int rc = to_dev(ctx, box_off, (size_t)nq + 1, &dbo);
-  fr.p[0] = dbo;
-  if (!rc) { rc = to_dev(ctx, time_off, (size_t)nq + 1, &dto); fr.p[1] = dto; }
-  if (!rc) { rc = to_dev(ctx, xy, (size_t)nbox * 4, &dxy); fr.p[2] = dxy; }
-  if (!rc) { rc = to_dev(ctx, t, (size_t)ntim * 2, &dt); fr.p[3] = dt; }
+  DevTemps tmp(s);
+  int rc = to_dev(ctx, tmp, box_off, (size_t)nq + 1, &dbo);
+  if (!rc) rc = to_dev(ctx, tmp, time_off, (size_t)nq + 1, &dto);
+  if (!rc) rc = to_dev(ctx, tmp, xy, (size_t)nbox * 4, &dxy);
+  if (!rc) rc = to_dev(ctx, tmp, t, (size_t)ntim * 2, &dt);
   if (rc) return rc;
   ZRangesArgs a{};
   a.box_off = dbo; a.xy = dxy; a.time_off = dto; a.t = dt;
@@ -1201,10 +1177,9 @@ int gm_z2_ranges(gm_ctx* ctx, int64_t nq, const int32_t* box_off, const double* 
   const int64_t nbox = box_off[nq];
   int32_t* dbo = nullptr;
   double* dxy = nullptr;
-  StreamFrees fr(s);
-  int rc = to_dev(ctx, box_off, (size_t)nq + 1, &dbo);
-  fr.p[0] = dbo;
-  if (!rc) { rc = to_dev(ctx, xy, (size_t)nbox * 4, &dxy); fr.p[1] = dxy; }
+  DevTemps tmp(s);
+  int rc = to_dev(ctx, tmp, box_off, (size_t)nq + 1, &dbo);
+  if (!rc) rc = to_dev(ctx, tmp, xy, (size_t)nbox * 4, &dxy);
   if (rc) return rc;
   ZRangesArgs a{};
   a.box_off = dbo; a.xy = dxy; a.time_off = nullptr; a.t = nullptr;
@@ -1235,10 +1210,9 @@ static int xz_ranges(gm_ctx* ctx, int D, int64_t nq, const int32_t* win_off, con
   const int64_t nw = win_off[nq];
   int32_t* dwo = nullptr;
   double* dw = nullptr;
-  StreamFrees fr(s);
-  int rc = to_dev(ctx, win_off, (size_t)nq + 1, &dwo);
-  fr.p[0] = dwo;
-  if (!rc) { rc = to_dev(ctx, windows, (size_t)nw * 2 * D, &dw); fr.p[1] = dw; }
+  DevTemps tmp(s);
+  int rc = to_dev(ctx, tmp, win_off, (size_t)nq + 1, &dwo);
+  if (!rc) rc = to_dev(ctx, tmp, windows, (size_t)nw * 2 * D, &dw);
   if (rc) return rc;
   XZWaveArgs a{};
   a.win_off = dwo; a.win = dw; a.g = g; a.zhi = (double)max_offset(period);
@@ -1286,10 +1260,9 @@ int gm_zranges(gm_ctx* ctx, int dims, int64_t nq, const int32_t* bound_off, cons
   if (nb > 0 && !zbounds) return GM_E_INVALID;
   int32_t* dbo = nullptr;
   int64_t* dzb = nullptr;
-  StreamFrees fr(s);
-  int rc = to_dev(ctx, bound_off, (size_t)nq + 1, &dbo);
-  fr.p[0] = dbo;
-  if (!rc) { rc = to_dev(ctx, zbounds, (size_t)nb * 2, &dzb); fr.p[1] = dzb; }
+  DevTemps tmp(s);
+  int rc = to_dev(ctx, tmp, bound_off, (size_t)nq + 1, &dbo);
+  if (!rc) rc = to_dev(ctx, tmp, zbounds, (size_t)nb * 2, &dzb);
   if (rc) return rc;
   ZRangesArgs a{};
   a.zb_off = dbo; a.zb = dzb;

@@ -190,7 +190,6 @@ struct ScanBufs {
 // pass A outputs (mask words + per-block counts) and a descriptor area, carved from the context's
 // scan workspace; user_mask, when given, receives the mask instead
 int alloc_scan(gm_ctx* ctx, int64_t n, uint64_t* user_mask, size_t desc_words, ScanBufs& b);
-void free_scan(gm_ctx* ctx, uint64_t* user_mask, ScanBufs& b);
 // passes B and C: block-count scan, ids in ascending row order, match count readback
 int finish_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_cap, int64_t* n_match);
 

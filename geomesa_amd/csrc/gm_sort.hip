@@ -68,31 +68,12 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
   return lane ? (~0ull >> (64 - lane)) : 0ull;
 }
 
-// The caller's columns, read two rows per lane (16-B z, 4-B bin, 2-B shard loads) when `vec` (aligned
-// columns) and both rows exist, else row by row.  bs = bin | shard << 16.
+// The caller's columns.  bs = bin | shard << 16.
 struct KeyCols {
   const uint8_t* sh;
   const uint16_t* bin;
   const uint64_t* z;
 };
-template <bool SH>
-__device__ __forceinline__ void load_pair(const KeyCols& c, int64_t i, int64_t n, bool vec, uint64_t& z0, uint64_t& z1,
-                                          uint32_t& bs0, uint32_t& bs1) {
-  if (vec && i + 1 < n) {
-    const ulonglong2 zz = *(const ulonglong2*)(c.z + i);
-    const uint32_t bb = *(const uint32_t*)(c.bin + i);
-    z0 = zz.x; z1 = zz.y;
-    bs0 = bb & 0xffffu; bs1 = bb >> 16;
-    if (SH) {
-      const uint32_t ss = *(const uint16_t*)(c.sh + i);
-      bs0 |= (ss & 0xffu) << 16; bs1 |= (ss >> 8) << 16;
-    }
-  } else {
-    z0 = z1 = 0; bs0 = bs1 = 0;
-    if (i < n) { z0 = c.z[i]; bs0 = (uint32_t)c.bin[i] | (SH ? (uint32_t)c.sh[i] << 16 : 0u); }
-    if (i + 1 < n) { z1 = c.z[i + 1]; bs1 = (uint32_t)c.bin[i + 1] | (SH ? (uint32_t)c.sh[i + 1] << 16 : 0u); }
-  }
-}
 
 // which digit passes carry information: the OR and the AND of every key column (a digit on which
 // OR == AND is the same for every key, so its pass would be the identity and is skipped).
@@ -230,11 +211,12 @@ __global__ __launch_bounds__(CT) void k_sort_count(KeyCols c, int64_t n, DigitOf
 
 // One-sweep digit pass over a digit of w <= 9 bits.  Block b takes tile k (the next in a counter, so
 // every lower tile is already running) of 8192 rows; wave w owns rows [512 w, 512 w + 512) of it and
-// reads them in 4 slots of 128 rows, 2 per lane.  Within a slot, lanes holding the same digit find each
-// other with 2 w ballots (w digit bits x even / odd row); a per-wave LDS counter per digit turns slot
-// ranks into wave ranks, a scan over the waves into tile ranks, so a row's place in the tile is
-// (digit, wave, slot, lane, even / odd) = stable.  The tile's digit offsets in the output are the
-// digit's global start plus its rows in every lower tile: thread d publishes digit d's tile count as
+// reads them in 4 slots of 128 rows, 2 per lane (rows r and r + 64: two halves of 64 consecutive rows).
+// Within a half, lanes holding the same digit find each other through a 64-bit LDS slot per digit; a
+// per-wave LDS counter per digit turns half ranks into wave ranks, a scan over the waves into tile
+// ranks, so a row's place in the tile is (digit, wave, slot, half, lane) = stable.  The tile's digit
+// offsets in the output are the digit's global start plus its rows in every lower tile: thread d
+// publishes digit d's tile count as
 // soon as the tile is ranked ({count, AGG} granule, one 8-B write-through store), then walks back over
 // the lower tiles' granules, adding counts until it meets an inclusive prefix (PRE), and publishes its
 // own (decoupled look-back).  The tile is reordered in LDS meanwhile and leaves as digit runs of 16-B
@@ -256,12 +238,6 @@ constexpr uint64_t GR_VAL = (1ull << 48) - 1;
 #define GM_SORT_LB 4
 #endif
 constexpr int LB = GM_SORT_LB;   // look-back granules per round trip
-#ifndef GM_SORT_SPLIT
-#define GM_SORT_SPLIT 1
-#endif
-#ifndef GM_SORT_LDSMATCH
-#define GM_SORT_LDSMATCH 1
-#endif
 
 struct PassArgs {
   KeyCols in;             // the caller's columns (first pass) ...
@@ -298,11 +274,10 @@ __global__ __launch_bounds__(PT) void k_sort_pass(PassArgs a) {
   for (int i = t; i < PW * NB_MAX / 2; i += PT) ((uint32_t*)&s_wcnt[0][0])[i] = 0u;
   __syncthreads();
   const int64_t tile = s_tile, t0 = tile * PTILE, n = a.n;
-#if GM_SORT_SPLIT
   // this lane's rows: slot k of wave w holds rows r = t0 + 512 w + 128 k + lane (A) and r + 64 (B), so
   // in input order a slot is its 64 A rows, then its 64 B rows, and each half ranks like one row per
-  // lane: 9 ballots and one mask per row.  (Round 5's pairs (2 lane, 2 lane + 1) interleave the halves
-  // and needed four cross masks per pair: ~80 instead of ~45 VALU per row in the ranking.)
+  // lane, with one mask per row.  (Pairs (2 lane, 2 lane + 1) would interleave the halves and need four
+  // cross masks per pair: ~80 instead of ~45 VALU per row with ballots, profiles/r6.)
   uint4 rv[PSLOT][2];
   const bool full = t0 + PTILE <= n;   // every tile but the last (uniform)
   const bool vec = a.vec && full;
@@ -342,14 +317,13 @@ __global__ __launch_bounds__(PT) void k_sort_pass(PassArgs a) {
   }
   const uint64_t lt = lanemask_lt();
   uint32_t rd[PSLOT][2];   // wave rank | digit << 16; rank 0xffff = no row
-#if GM_SORT_LDSMATCH
   // lanes sharing a digit found through LDS instead of 9 ballot rounds: each row ORs its lane bit into
   // its digit's 64-bit slot, reads the slot back, and clears it.  The slots (512 per wave, 64 KB) alias
   // s_rec, which is written only after the ranking's barrier.
+  static_assert(PW * NB_MAX * sizeof(uint64_t) <= sizeof(uint4) * PTILE, "digit-match slots alias s_rec");
   uint64_t* mslot = (uint64_t*)s_rec + wave * NB_MAX;
   for (int j = lane; j < NB_MAX; j += 64) mslot[j] = 0ull;
   wave_lds_sync();
-#endif
 #pragma unroll
   for (int k = 0; k < PSLOT; ++k)
 #pragma unroll
@@ -357,20 +331,11 @@ __global__ __launch_bounds__(PT) void k_sort_pass(PassArgs a) {
       const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 64 * e + lane;
       const bool ok = i < n;
       const uint32_t d = key_digit_w(rv[k][e].w, rec_z(rv[k][e]), a.off, w);
-#if GM_SORT_LDSMATCH
       if (ok) atomicOr((unsigned long long*)&mslot[d], 1ull << lane);
       wave_lds_sync();
       const uint64_t m = ok ? mslot[d] : 0ull;   // lanes of this half whose row holds my row's digit
       wave_lds_sync();
       if (ok) mslot[d] = 0ull;
-#else
-      uint64_t m = __ballot(ok);   // lanes of this half whose row holds my row's digit
-#pragma unroll
-      for (int bit = 0; bit < WMAX; ++bit) {   // bits at or above w are 0 in every digit: no-op rounds
-        const uint64_t bb = __ballot((d >> bit) & 1u);
-        m &= ((d >> bit) & 1u) ? bb : ~bb;
-      }
-#endif
       const int r = __popcll(m & lt);
       // the wave's counter: read before this half's increment, then the first row of each digit adds
       const uint32_t c = s_wcnt[wave][d];
@@ -379,86 +344,6 @@ __global__ __launch_bounds__(PT) void k_sort_pass(PassArgs a) {
       if (ok && r == 0) s_wcnt[wave][d] = (uint16_t)(c + __popcll(m));
       __builtin_amdgcn_wave_barrier();
     }
-#else
-  // this lane's rows
-  uint4 rv[PSLOT][2];
-  const bool full = t0 + PTILE <= n;   // every tile but the last (uniform)
-  const bool vec = a.vec && full;
-  if (IN_REC && full) {
-    // a full tile's loads are unconditional, so the compiler counts them: all 2 * PSLOT are in flight
-    // before the first wait.  (Under the per-row `i < n` selects each load sat in its own branch and
-    // was waited for before the next one was issued: one load in flight per lane.)
-#pragma unroll
-    for (int k = 0; k < PSLOT; ++k) {
-      const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 2 * lane;
-      rv[k][0] = a.rec_in[i];
-      rv[k][1] = a.rec_in[i + 1];
-    }
-  } else if (!IN_REC && vec) {   // the same for the first pass's column loads
-#pragma unroll
-    for (int k = 0; k < PSLOT; ++k) {
-      const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 2 * lane;
-      const ulonglong2 zz = *(const ulonglong2*)(a.in.z + i);
-      uint32_t bb = *(const uint32_t*)(a.in.bin + i);
-      uint32_t b0 = bb & 0xffffu, b1 = bb >> 16;
-      if (SH) {
-        const uint32_t ss = *(const uint16_t*)(a.in.sh + i);
-        b0 = squeeze_bs(b0 | (ss & 0xffu) << 16, a.sq); b1 = squeeze_bs(b1 | (ss >> 8) << 16, a.sq);
-      }
-      rv[k][0] = make_rec(zz.x, (uint32_t)i, b0);
-      rv[k][1] = make_rec(zz.y, (uint32_t)(i + 1), b1);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PSLOT; ++k) {
-      const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 2 * lane;
-      if (IN_REC) {
-        rv[k][0] = i < n ? a.rec_in[i] : make_uint4(0u, 0u, 0u, 0u);
-        rv[k][1] = i + 1 < n ? a.rec_in[i + 1] : make_uint4(0u, 0u, 0u, 0u);
-      } else {
-        uint64_t z0, z1;
-        uint32_t b0, b1;
-        load_pair<SH>(a.in, i, n, vec, z0, z1, b0, b1);
-        if (SH) { b0 = squeeze_bs(b0, a.sq); b1 = squeeze_bs(b1, a.sq); }
-        rv[k][0] = make_rec(z0, (uint32_t)i, b0);
-        rv[k][1] = make_rec(z1, (uint32_t)(i + 1), b1);
-      }
-    }
-  }
-  const uint64_t lt = lanemask_lt();
-  uint32_t rd[PSLOT][2];   // wave rank | digit << 16; rank 0xffff = no row
-#pragma unroll
-  for (int k = 0; k < PSLOT; ++k) {
-    const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 2 * lane;
-    const bool ok0 = i < n, ok1 = i + 1 < n;
-    const uint32_t d0 = key_digit_w(rv[k][0].w, rec_z(rv[k][0]), a.off, w);
-    const uint32_t d1 = key_digit_w(rv[k][1].w, rec_z(rv[k][1]), a.off, w);
-    // masks of lanes whose even / odd row holds my even / odd row's digit
-    uint64_t m00 = __ballot(ok0), m01 = __ballot(ok1);
-    uint64_t m10 = m00, m11 = m01;
-#pragma unroll
-    for (int bit = 0; bit < WMAX; ++bit) {
-      if (bit < w) {   // wave-uniform
-        const uint64_t b0 = __ballot((d0 >> bit) & 1u), b1 = __ballot((d1 >> bit) & 1u);
-        m00 &= ((d0 >> bit) & 1u) ? b0 : ~b0;
-        m01 &= ((d0 >> bit) & 1u) ? b1 : ~b1;
-        m10 &= ((d1 >> bit) & 1u) ? b0 : ~b0;
-        m11 &= ((d1 >> bit) & 1u) ? b1 : ~b1;
-      }
-    }
-    const uint64_t le = lt | (1ull << lane);
-    const int r0 = __popcll(m00 & lt) + __popcll(m01 & lt);
-    const int r1 = __popcll(m10 & le) + __popcll(m11 & lt);
-    // wave counters: read before this slot's increments, then the first row of each digit adds
-    const uint32_t c0 = s_wcnt[wave][d0], c1 = s_wcnt[wave][d1];
-    rd[k][0] = (ok0 ? c0 + r0 : 0xffffu) | (d0 << 16);
-    rd[k][1] = (ok1 ? c1 + r1 : 0xffffu) | (d1 << 16);
-    __builtin_amdgcn_wave_barrier();
-    if (ok0 && r0 == 0) s_wcnt[wave][d0] = (uint16_t)(c0 + __popcll(m00) + __popcll(m01));
-    if (ok1 && r1 == 0) s_wcnt[wave][d1] = (uint16_t)(c1 + __popcll(m10) + __popcll(m11));
-    __builtin_amdgcn_wave_barrier();
-  }
-#endif
   __syncthreads();
   // thread t owns digit t (t < nb): wave offsets, the tile total, scans of totals and global counts
   uint32_t tot = 0, xt = 0, xb = 0, cg = 0;
@@ -1056,16 +941,18 @@ int gm_sort_keys(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const in
   if (!bin) {
     // no time bin (Z2 / XZ2 tables): the sort runs over a zero bin column (constant, so no digit pass
     // looks at it) and its bin output goes to scratch
-    void* zb = nullptr;
-    int rc = ctx_workspace(ctx, WS_SCAN, (((size_t)n * 2 + 15) & ~(size_t)15) * 2, &zb);
+    Carve c{16};
+    const size_t o_in = c.take((size_t)n * 2), o_out = c.take((size_t)n * 2);
+    char* zb = nullptr;
+    int rc = ctx_workspace(ctx, WS_SCAN, c.total, (void**)&zb);
     if (rc) return rc;
-    bin = (const int16_t*)zb;
-    bin_out = (int16_t*)((char*)zb + (((size_t)n * 2 + 15) & ~(size_t)15));
-    GM_HIP(hipMemsetAsync(zb, 0, (size_t)n * 2, s));
+    bin = (const int16_t*)(zb + o_in);
+    bin_out = (int16_t*)(zb + o_out);
+    GM_HIP(hipMemsetAsync(zb + o_in, 0, (size_t)n * 2, s));
   }
   const uint8_t* sh = shard;
   const KeyCols in{sh, (const uint16_t*)bin, (const uint64_t*)z};
-  // 16-B z / 4-B bin / 2-B shard pair loads need aligned caller columns
+  // aligned caller columns: the first pass then loads a full tile's rows unconditionally
   const int user_vec = ((uintptr_t)z % 16) == 0 && ((uintptr_t)bin % 4) == 0 && (!sh || ((uintptr_t)sh % 2) == 0);
   // 16-B loads of every column in the OR/AND and count reads
   const int user_wide = ((uintptr_t)z % 16) == 0 && ((uintptr_t)bin % 16) == 0 && (!sh || ((uintptr_t)sh % 16) == 0);
@@ -1082,21 +969,21 @@ int gm_sort_keys(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const in
   int64_t* lbounds = nullptr;
   size_t counts_bytes = 0;
   {  // context-owned workspace: records x 2 | granules | counts | tile counters | local bounds, 16-B aligned
-    auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t a_r = al((size_t)n * 16), a_st = al((size_t)ntiles * NB_MAX * 8), a_c = al((size_t)MAXTAG * NB_MAX * 4),
-                 a_t = al((size_t)MAXTAG * 4), a_b = al((size_t)((n + LSTEP - 1) / LSTEP + 1) * 8);
-    void* base = nullptr;
-    int wrc = ctx_workspace(ctx, WS_SORT, 2 * a_r + a_st + a_c + a_t + a_b, &base);
+    Carve c{16};
+    const size_t o_r0 = c.take((size_t)n * 16), o_r1 = c.take((size_t)n * 16), o_st = c.take((size_t)ntiles * NB_MAX * 8),
+                 o_c = c.take((size_t)MAXTAG * NB_MAX * 4), o_t = c.take((size_t)MAXTAG * 4),
+                 o_b = c.take((size_t)((n + LSTEP - 1) / LSTEP + 1) * 8);
+    char* base = nullptr;
+    int wrc = ctx_workspace(ctx, WS_SORT, c.total, (void**)&base);
     if (wrc) return wrc;
-    char* q = (char*)base;
-    rec[0] = (uint4*)q; q += a_r;
-    rec[1] = (uint4*)q; q += a_r;
-    status = (unsigned long long*)q; q += a_st;
-    counts = (uint32_t*)q; q += a_c;
-    ctr = (unsigned int*)q; q += a_t;
-    lbounds = (int64_t*)q;
-    counts_bytes = a_c;
-    GM_HIP(hipMemsetAsync(status, 0, a_st + a_c + a_t, s));   // granules (tag 0 = none), counts, counters
+    rec[0] = (uint4*)(base + o_r0);
+    rec[1] = (uint4*)(base + o_r1);
+    status = (unsigned long long*)(base + o_st);
+    counts = (uint32_t*)(base + o_c);
+    ctr = (unsigned int*)(base + o_t);
+    lbounds = (int64_t*)(base + o_b);
+    counts_bytes = o_t - o_c;
+    GM_HIP(hipMemsetAsync(status, 0, o_b - o_st, s));   // granules (tag 0 = none), counts, counters: adjacent
   }
   // which key bits vary: acc[0..3] = OR z, OR bs, AND z, AND bs of every key (k_sort_count), acc[8..11]
   // the same over a sample (k_key_or_and_sample), acc[4] k_sort_local's flag
@@ -1249,18 +1136,17 @@ int gm_key_partition(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, cons
   hipStream_t s = ctx->stream;
   const int64_t ntiles = (n + XTILE - 1) / XTILE, ncnt = ntiles * nd;
   // workspace: splitters | counts (u32, destination-major) | their scan (i64) | scan partials | totals
-  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t a_s = al((size_t)std::max(1, n_split) * 16), a_c = al((size_t)ncnt * 4), a_o = al((size_t)ncnt * 8),
-               a_p = al((size_t)scan_partials_len(ncnt) * 8), a_t = al((size_t)(nd + 1) * 8);
-  void* base = nullptr;
-  int rc = ctx_workspace(ctx, WS_SCAN, a_s + a_c + a_o + a_p + a_t, &base);
+  Carve c{16};
+  const size_t o_s = c.take((size_t)std::max(1, n_split) * 16), o_c = c.take((size_t)ncnt * 4), o_o = c.take((size_t)ncnt * 8),
+               o_p = c.take((size_t)scan_partials_len(ncnt) * 8), o_t = c.take((size_t)(nd + 1) * 8);
+  char* base = nullptr;
+  int rc = ctx_workspace(ctx, WS_SCAN, c.total, (void**)&base);
   if (rc) return rc;
-  char* q = (char*)base;
-  uint64_t* split = (uint64_t*)q; q += a_s;
-  uint32_t* cnt = (uint32_t*)q; q += a_c;
-  int64_t* offs = (int64_t*)q; q += a_o;
-  int64_t* partials = (int64_t*)q; q += a_p;
-  int64_t* dtot = (int64_t*)q;   // [nd] destination totals, then the scan's grand total
+  uint64_t* split = (uint64_t*)(base + o_s);
+  uint32_t* cnt = (uint32_t*)(base + o_c);
+  int64_t* offs = (int64_t*)(base + o_o);
+  int64_t* partials = (int64_t*)(base + o_p);
+  int64_t* dtot = (int64_t*)(base + o_t);   // [nd] destination totals, then the scan's grand total
   if (n_split > 0) {
     std::vector<uint64_t> hs((size_t)n_split * 2);
     for (int32_t k = 0; k < n_split; ++k) { hs[2 * (size_t)k] = split_hi[k]; hs[2 * (size_t)k + 1] = split_lo[k]; }
