@@ -66,13 +66,13 @@ class KeyRange(ctypes.Structure):
 
 class ScanFilter(ctypes.Structure):
     """gm_scan_filter: the row filter (Z3Filter or Z2Filter bytes) and the full filter (envelopes x boxes,
-    dtg during) of gm_table_scan."""
+    dtg during) of gm_table_scan; rows maps a table row to its row of the full filter's columns."""
     _fields_ = [("z3filter", ctypes.c_void_p), ("z3filter_len", ctypes.c_size_t),
                 ("z2filter", ctypes.c_void_p), ("z2filter_len", ctypes.c_size_t),
                 ("xmin", ctypes.c_void_p), ("ymin", ctypes.c_void_p), ("xmax", ctypes.c_void_p),
                 ("ymax", ctypes.c_void_p), ("boxes", ctypes.c_void_p), ("n_boxes", ctypes.c_int32),
                 ("during", ctypes.c_int32), ("t_ms", ctypes.c_void_p), ("t_lo", ctypes.c_int64),
-                ("t_hi", ctypes.c_int64)]
+                ("t_hi", ctypes.c_int64), ("rows", ctypes.c_void_p)]
 
 
 # numpy view of gm_key_range rows (24 B, the KeyRange layout)

@@ -475,16 +475,17 @@ __device__ __forceinline__ int64_t cand_row(const int64_t* __restrict__ coff, co
 // filter the tablet server runs on the key (RowFilterIterator.scala:52-66): none, Z3Filter.inBounds on
 // (bin, z) (Z3Filter.scala:26-62) or Z2Filter.inBounds on z (Z2Filter.scala:20-35).  ENV / DUR: the full
 // filter on the feature (the XZ key spaces' useFullFilter = true, XZ2IndexKeySpace.scala:122-125,
-// XZ3IndexKeySpace.scala:247-250) over the caller's input-order columns, reached through perm: JTS
-// Envelope.intersects with any query box (inclusive), and FastDuring (exclusive, ms) on the dtg.
+// XZ3IndexKeySpace.scala:247-250) over the caller's feature columns, reached through `rows` (table row ->
+// column row; not the id map k_cand_to_row applies): JTS Envelope.intersects with any query box
+// (inclusive), and FastDuring (exclusive, ms) on the dtg.
 enum : int { RF_NONE = 0, RF_Z3 = 1, RF_Z2 = 2 };
 struct FullFilter {
-  const double *xmin, *ymin, *xmax, *ymax;   // feature envelopes (input order)
-  const int64_t* t;                           // feature dtg (input order)
+  const double *xmin, *ymin, *xmax, *ymax;   // feature envelopes (column order)
+  const int64_t* t;                           // feature dtg (column order)
   const double* boxes;                        // nbox x (xmin, ymin, xmax, ymax), device
   int nbox;
   int64_t t_lo, t_hi;
-  const int64_t* perm;                        // table row -> input row (null: the identity)
+  const int64_t* rows;                        // table row -> column row (null: the identity)
 };
 // JTS Envelope.intersects(Envelope): false for a null envelope (maxx < minx) on either side
 __device__ __forceinline__ bool env_intersects(double ax0, double ay0, double ax1, double ay1, const double* q) {
@@ -519,7 +520,7 @@ __global__ __launch_bounds__(FTPB) void k_range_mask(const uint16_t* __restrict_
           ok = in;
         }
         if ((ENV || DUR) && ok) {
-          const int64_t r = ff.perm ? ff.perm[row] : row;
+          const int64_t r = ff.rows ? ff.rows[row] : row;
           if (DUR) {
             const int64_t t = ff.t[r];
             ok = t > ff.t_lo && t < ff.t_hi;
@@ -969,7 +970,7 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
       GM_HIP(hipStreamSynchronize(s));
     }
     FullFilter ff{f->xmin, f->ymin, f->xmax, f->ymax, f->t_ms, env ? (const double*)b.desc : nullptr, f->n_boxes,
-                  f->t_lo, f->t_hi, perm};
+                  f->t_lo, f->t_hi, f->rows ? f->rows : perm};
     const int32_t* d_desc = b.desc + box_words;
     const int64_t nblocks = (total + FROWS - 1) / FROWS;
     void (*kern)(const uint16_t*, const uint64_t*, const int64_t*, const int64_t*, int64_t, int64_t, const int32_t*,
@@ -984,8 +985,8 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
     GM_CHECK_LAUNCH();
     rc = finish_scan(ctx, total, b, ids, ids_cap, &nm);
     if (rc) return rc;
-    if (ids && nm > 0) {
-      const int64_t m = std::min(nm, ids_cap);
+    const int64_t m = std::min(nm, ids_cap);
+    if (ids && m > 0) {
       hipLaunchKernelGGL(k_cand_to_row, dim3((unsigned)std::min<int64_t>(4096, (m + FTPB - 1) / FTPB)), dim3(FTPB), 0,
                          s, ids, m, coff, start, nr, perm);
       GM_CHECK_LAUNCH();

@@ -318,11 +318,15 @@ class _KeyTable:
         return ids[:min(nm.value, cap)], nm.value, ns.value
 
 
-def _full_filter(cols, boxes, interval=None, t=None):
-    """ScanFilter for the XZ full filter: envelope columns x boxes, dtg during (lo, hi) exclusive.  The
-    host arrays it points to are returned beside it (they must outlive the call)."""
+def _full_filter(cols, boxes, interval=None, t=None, perm=None):
+    """ScanFilter for the XZ full filter: envelope columns x boxes, dtg during (lo, hi) exclusive.  cols
+    and t are in input order and perm (the table's) takes a table row to them, whatever the scan maps its
+    ids through.  The host arrays the filter points to are returned beside it (they must outlive the
+    call)."""
     f = _lib.ScanFilter()
     keep = []
+    if perm is not None:
+        f.rows = perm.data_ptr()
     if boxes:
         bx = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
         keep.append(bx)
@@ -353,7 +357,7 @@ class Z2Table(_KeyTable):
             return torch.zeros(0, dtype=torch.int64, device=self.z.device), 0, 0
         arr, _ = key_ranges(self.ks.get_ranges(v, target=target), self.shards)
         if strict:
-            f, keep = _full_filter((self.x, self.y, self.x, self.y), v.spatialBounds)
+            f, keep = _full_filter((self.x, self.y, self.x, self.y), v.spatialBounds, perm=self.perm)
         else:
             fb = F.serialize_to_bytes(F.Z2Filter.from_values(v))
             keep = [ctypes.create_string_buffer(fb, len(fb))]
@@ -381,7 +385,7 @@ class XZ2Table(_KeyTable):
             import torch
             return torch.zeros(0, dtype=torch.int64, device=self.z.device), 0, 0
         arr, _ = key_ranges(self.ks.get_ranges(v, target=target), self.shards)
-        f, keep = _full_filter(self.env, v.spatialBounds) if full_filter else (None, [])
+        f, keep = _full_filter(self.env, v.spatialBounds, perm=self.perm) if full_filter else (None, [])
         return self.table_scan(arr, f)
 
 
@@ -416,5 +420,5 @@ class XZ3Table(_KeyTable):
             import torch
             return torch.zeros(0, dtype=torch.int64, device=self.z.device), 0, 0
         arr, _ = key_ranges(self.ks.get_ranges(v, target=target), self.shards)
-        f, keep = _full_filter(self.env, v.spatialBounds, interval, self.t) if full_filter else (None, [])
+        f, keep = _full_filter(self.env, v.spatialBounds, interval, self.t, self.perm) if full_filter else (None, [])
         return self.table_scan(arr, f)

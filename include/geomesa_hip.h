@@ -527,13 +527,18 @@ int gm_key_range_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
      20-35), not both;
    - the full filter on the feature, which the XZ key spaces always apply (useFullFilter = true,
      XZ2IndexKeySpace.scala:122-125, XZ3IndexKeySpace.scala:247-250): with n_boxes > 0 the feature's
-     envelope (xmin / ymin / xmax / ymax: device columns in INPUT order, reached through perm)
-     intersects at least one of the boxes (host, n_boxes x (xmin, ymin, xmax, ymax); JTS
-     Envelope.intersects, inclusive; a null envelope -- max < min -- never intersects), and with
-     during != 0 the feature's dtg (t_ms: device, input order) lies in (t_lo, t_hi), exclusive
-     (FastDuring, FastTemporalOperator.scala:116-129).  For a rectangular geometry the envelope test is
-     GeoTools BBOX exactly; for other geometries it is BBOX's envelope pre-check (geometry-geometry
-     relations are out of scope). */
+     envelope (xmin / ymin / xmax / ymax: device columns, reached through rows) intersects at least
+     one of the boxes (host, n_boxes x (xmin, ymin, xmax, ymax); JTS Envelope.intersects, inclusive; a
+     null envelope -- maxx < minx, JTS Envelope.isNull, on either side -- never intersects; the y
+     ends and NaN take no part in that rule), and with during != 0 the feature's dtg (t_ms: device, same
+     order as the envelopes) lies in (t_lo, t_hi), exclusive (FastDuring,
+     FastTemporalOperator.scala:116-129).  For a rectangular geometry the envelope test is GeoTools
+     BBOX exactly; for other geometries it is BBOX's envelope pre-check (geometry-geometry relations
+     are out of scope);
+   - rows (device, optional): the column row of each table row, i.e. where table row r's envelope and
+     dtg are found (xmin[rows[r]], ...).  NULL: gm_table_scan's perm argument maps them (columns in
+     INPUT order); both NULL: the columns are in table order.  rows only reaches the full filter's
+     columns; the ids that come back are mapped by perm alone. */
 typedef struct {
   const uint8_t* z3filter;
   size_t z3filter_len;
@@ -549,6 +554,7 @@ typedef struct {
   const int64_t* t_ms;
   int64_t t_lo;
   int64_t t_hi;
+  const int64_t* rows;
 } gm_scan_filter;
 /* Seek-and-filter over any sorted key table (gm_sort_keys order): Z3 and XZ3 tables ([shard][bin][z]),
    Z2 and XZ2 tables (bin = NULL: [shard][z]).  Every row inside any of the ranges (host array, merged as

@@ -606,17 +606,52 @@ def key_partition(shard, bins, zs, sp_hi, sp_lo):
     return order, np.bincount(dest, minlength=len(sp_hi) + 1).astype(np.int64)
 
 
+# ---------------------------------------------------------------- the seek of a table scan
+def table_scan_rows(shard, bins, z, ranges):
+    """The definition of gm_table_scan's candidates: the mask over the rows of a SORTED table (columns in
+    gm_sort_keys order; shard / bins None: absent, read as 0) whose key lies in any of `ranges` (gm_key_range
+    rows: a structured array or anything with z_lo, z_hi, bin_lo, bin_hi, shard fields).  A key is the
+    pair of table_key_u64, (shard << 16 | bin as u16, z as u64), compared unsigned and lexicographically; both
+    ends of a range are inclusive; a range whose hi key is below its lo key holds nothing.  No sorting, no
+    merging: the mask is the union, so a scan's n_scanned is mask.sum()."""
+    z = np.asarray(z)
+    n = len(z)
+    hi, lo = table_key_u64(shard, np.zeros(n, np.int16) if bins is None else bins, z)
+    mask = np.zeros(n, bool)
+    if len(ranges) == 0 or n == 0:
+        return mask
+    rsh, nr = np.asarray(ranges["shard"]), len(ranges)
+    lo_hi, lo_lo = table_key_u64(rsh, ranges["bin_lo"], ranges["z_lo"])
+    hi_hi, hi_lo = table_key_u64(rsh, ranges["bin_hi"], ranges["z_hi"])
+    # dense rank of every key in play (rows, lo ends, hi ends; equal keys share a rank), so that the
+    # 88-bit comparisons become integer ones; the rows' own order is never used
+    all_hi, all_lo = np.concatenate([hi, lo_hi, hi_hi]), np.concatenate([lo, lo_lo, hi_lo])
+    order = np.lexsort((all_lo, all_hi))
+    s_hi, s_lo = all_hi[order], all_lo[order]
+    step = np.concatenate([[0], ((s_hi[1:] != s_hi[:-1]) | (s_lo[1:] != s_lo[:-1])).astype(np.int64)])
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.cumsum(step)
+    r_row, r_lo, r_hi = rank[:n], rank[n:n + nr], rank[n + nr:]
+    live = r_hi >= r_lo   # hi < lo in key order: an empty range
+    cover = np.zeros(int(rank.max()) + 2, np.int64)
+    np.add.at(cover, r_lo[live], 1)
+    np.add.at(cover, r_hi[live] + 1, -1)
+    return np.cumsum(cover)[r_row] > 0
+
+
 # ---------------------------------------------------------------- the XZ full filter (full-scan restatement)
 def envelope_scan(xmin, ymin, xmax, ymax, boxes, t_ms=None, interval=None):
     """Mask of features whose envelope intersects any box (JTS Envelope.intersects: inclusive, a null
-    envelope -- max < min -- never intersects) AND, with an interval, whose dtg lies in (lo, hi) (FastDuring,
-    exclusive; FastTemporalOperator.scala:116-129): the full filter the XZ key spaces apply
-    (XZ2IndexKeySpace.scala:122-125, XZ3IndexKeySpace.scala:247-250), evaluated on every feature."""
+    envelope -- Envelope.isNull: maxx < minx, nothing else -- on either side never intersects, then
+    !(q.minx > maxx || q.maxx < minx || q.miny > maxy || q.maxy < miny), so an envelope inverted in y only
+    is decided by the comparisons and a NaN fails none of them) AND, with an interval, whose dtg lies in
+    (lo, hi) (FastDuring, exclusive; FastTemporalOperator.scala:116-129): the full filter the XZ key spaces
+    apply (XZ2IndexKeySpace.scala:122-125, XZ3IndexKeySpace.scala:247-250), evaluated on every feature."""
     xmin, ymin, xmax, ymax = (np.asarray(c, np.float64) for c in (xmin, ymin, xmax, ymax))
     ok = np.zeros(len(xmin), bool)
-    valid = ~((xmax < xmin) | (ymax < ymin))
+    valid = ~(xmax < xmin)
     for (bx0, by0, bx1, by1) in boxes:
-        if bx1 < bx0 or by1 < by0:
+        if bx1 < bx0:
             continue
         ok |= valid & ~((bx0 > xmax) | (bx1 < xmin) | (by0 > ymax) | (by1 < ymin))
     if interval is not None:

@@ -131,6 +131,12 @@ ADVERSARIAL_Z3 = [
 ]
 
 
+def adversarial_z2(k):
+    """The Z2Filter that goes with ADVERSARIAL_Z3[k]: whole-range, empty, small and negative boxes."""
+    return F.Z2Filter([[-2**31, -5, 2**31 - 1, 100], [10, 10, 5, 5], [0, 0, 1 << 20, 1 << 20],
+                       [-(1 << 30), -(1 << 31), -1, -1]][: k + 2])
+
+
 @pytest.mark.parametrize("k", range(len(ADVERSARIAL_Z3)))
 def test_filters_on_arbitrary_row_bits(gpu, oracle, k):
     """Dilated-bound fast paths vs the oracle on arbitrary 64-bit z words (sign bit, bit 62 and 63
@@ -145,8 +151,7 @@ def test_filters_on_arbitrary_row_bits(gpu, oracle, k):
         m, ids, cnt = F.scan(f, b, z, br, want_ids=True)
         om = oracle.z3filter_scan(F.serialize_to_bytes(f), br, b, z)
         assert np.array_equal(as_np(m), om) and cnt == int(om.sum())
-    f2 = F.Z2Filter([[-2**31, -5, 2**31 - 1, 100], [10, 10, 5, 5], [0, 0, 1 << 20, 1 << 20],
-                     [-(1 << 30), -(1 << 31), -1, -1]][: k + 2])
+    f2 = adversarial_z2(k)
     m, ids, cnt = F.z2_scan(f2, z, want_ids=True)
     om = oracle.z2filter_scan(F.z2_serialize_to_bytes(f2), z)
     assert np.array_equal(as_np(m), om) and np.array_equal(as_np(ids), np.nonzero(om)[0])
