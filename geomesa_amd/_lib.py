@@ -203,8 +203,15 @@ def last_error():
     return load().gm_last_error().decode(errors="replace")
 
 
-def check(rc, what):
-    if rc == GM_OK:
+# what a wrapper passes as check()'s `allow` when it gives a summary and may give no status[]
+ALLOW_ELEMENT = (GM_E_ELEMENT,)
+
+
+def check(rc, what, allow=()):
+    """Raises on a non-zero return code.  `allow` names codes the caller handles itself and lets through:
+    a wrapper that passes a summary without a status[] allows GM_E_ELEMENT and raises its
+    IllegalArgumentException from the summary."""
+    if rc == GM_OK or rc in allow:
         return
     raise GeomesaHipError("%s failed: rc=%d (%s)" % (what, rc, last_error()))
 

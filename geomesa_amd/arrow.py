@@ -25,7 +25,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import check, ptr
+from ._lib import ALLOW_ELEMENT as _ELEMENT, check, ptr
 from .curve import IllegalArgumentException, TimePeriod, _raise_first, _summary
 
 KINDS = {"point": 0, "linestring": 1, "polygon": 2, "multipoint": 3, "multilinestring": 4, "multipolygon": 5}
@@ -202,7 +202,7 @@ def z3_index_keys(points, dtg=None, period=TimePeriod.Week, lenient=False, statu
     check(ctx.lib.gm_z3_index_key_arrow(ctx.handle, ctypes.byref(g.c_struct()),
                                         ctypes.byref(t.c_struct()) if t is not None else None, n,
                                         TimePeriod.of(period), int(bool(lenient)), ptr(b), ptr(z), ptr(s),
-                                        ctypes.byref(st)), "gm_z3_index_key_arrow")
+                                        ctypes.byref(st)), "gm_z3_index_key_arrow", _ELEMENT)
     return _finish(st, "Z3IndexKeySpace.toIndexKey", s, (b, z))
 
 
@@ -218,7 +218,7 @@ def z2_index_keys(points, lenient=False, status=False, flip_axis=False):
     s = torch.empty(n, dtype=torch.uint8, device=g._coords.device) if status else None
     st = _summary()
     check(ctx.lib.gm_z2_index_key_arrow(ctx.handle, ctypes.byref(g.c_struct()), n, int(bool(lenient)), ptr(z),
-                                        ptr(s), ctypes.byref(st)), "gm_z2_index_key_arrow")
+                                        ptr(s), ctypes.byref(st)), "gm_z2_index_key_arrow", _ELEMENT)
     return _finish(st, "Z2IndexKeySpace.toIndexKey", s, (z,))
 
 
@@ -234,7 +234,7 @@ def xz2_index_keys(geoms, kind="polygon", g=12, lenient=False, status=False, fli
     s = torch.empty(n, dtype=torch.uint8, device=col._coords.device) if status else None
     st = _summary()
     check(ctx.lib.gm_xz2_index_key_arrow(ctx.handle, ctypes.byref(col.c_struct()), n, int(g), int(bool(lenient)),
-                                         ptr(xz), ptr(s), ctypes.byref(st)), "gm_xz2_index_key_arrow")
+                                         ptr(xz), ptr(s), ctypes.byref(st)), "gm_xz2_index_key_arrow", _ELEMENT)
     return _finish(st, "XZ2IndexKeySpace.toIndexKey", s, (xz,))
 
 
@@ -255,7 +255,7 @@ def xz3_index_keys(geoms, dtg=None, kind="polygon", g=12, period=TimePeriod.Week
     check(ctx.lib.gm_xz3_index_key_arrow(ctx.handle, ctypes.byref(col.c_struct()),
                                          ctypes.byref(t.c_struct()) if t is not None else None, n, int(g),
                                          TimePeriod.of(period), int(bool(lenient)), ptr(b), ptr(xz), ptr(s),
-                                         ctypes.byref(st)), "gm_xz3_index_key_arrow")
+                                         ctypes.byref(st)), "gm_xz3_index_key_arrow", _ELEMENT)
     return _finish(st, "XZ3IndexKeySpace.toIndexKey", s, (b, xz))
 
 

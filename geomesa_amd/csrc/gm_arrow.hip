@@ -442,7 +442,7 @@ int gm_z3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time
     default: launch_z3_arrow_p<YEAR>(s, vec, lenient, f32, g, tc, n, lon, lat, tim, bin, z, status, ctx->d_err); break;
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_z2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, int lenient, int64_t* z, uint8_t* status,
@@ -470,7 +470,7 @@ int gm_z2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, in
   }
 #undef GM_Z2A
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 static int xz_key_arrow(gm_ctx* ctx, int dim, const gm_geom_column* geom, const gm_time_column* dtg, int64_t n, int g,
@@ -498,7 +498,7 @@ static int xz_key_arrow(gm_ctx* ctx, int dim, const gm_geom_column* geom, const 
     }
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_xz2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, int g, int lenient, int64_t* xz,

@@ -151,7 +151,7 @@ int begin_summary(gm_ctx* ctx, gm_batch_status* summary) {
   return GM_OK;
 }
 
-int end_summary(gm_ctx* ctx, gm_batch_status* summary) {
+int end_summary(gm_ctx* ctx, gm_batch_status* summary, const uint8_t* status) {
   if (!summary) return GM_OK;
   GM_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_err, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   GM_HIP(hipStreamSynchronize(ctx->stream));
@@ -164,6 +164,10 @@ int end_summary(gm_ctx* ctx, gm_batch_status* summary) {
     summary->first_code = 0;
   }
   summary->reserved = 0;
+  if (summary->n_errors > 0 && !status) {
+    set_error("at least one element failed; see the summary");
+    return GM_E_ELEMENT;
+  }
   return GM_OK;
 }
 
@@ -424,6 +428,7 @@ int gm_gen_points(gm_ctx* c, uint64_t seed, int64_t n, int64_t base, double lon0
                   double lat1, int64_t t0, int64_t t1, double* x, double* y, int64_t* t) {
   if (!c || n < 0) return GM_E_INVALID;
   if (n == 0) return GM_OK;
+  if (!x && !y && !t) return GM_E_INVALID;   // each column is optional (the kernel skips a NULL one); none is an error
   hipLaunchKernelGGL(gm::k_gen_points, dim3(gm::grid_for(n, 256)), dim3(256), 0, c->stream, seed, n, base, lon0,
                      lon1, lat0, lat1, t0, t1, x, y, t);
   GM_CHECK_LAUNCH();

@@ -485,7 +485,7 @@ int gm_z3_index_key(gm_ctx* ctx, const double* x, const double* y, const int64_t
     default: launch_key_p<YEAR>(ctx->stream, x, y, t_ms, n, bin, z, status, lon, lat, tim, ctx->d_err, lenient, vec); break;
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_z3_index(gm_ctx* ctx, const double* x, const double* y, const int64_t* t, int64_t n, int period,
@@ -505,7 +505,7 @@ int gm_z3_index(gm_ctx* ctx, const double* x, const double* y, const int64_t* t,
     else hipLaunchKernelGGL((k_z3_index<false, false>), dim3(grid), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status, lon, lat, tim, ctx->d_err);
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_z3_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int period, int precision, double* x, double* y,
@@ -557,7 +557,7 @@ int gm_z2_index(gm_ctx* ctx, const double* x, const double* y, int64_t n, int pr
     }
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_z2_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int precision, double* x, double* y) {
@@ -596,7 +596,7 @@ int gm_binned_time(gm_ctx* ctx, const int64_t* t_ms, int64_t n, int period, int1
   }
 #undef GM_BT
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_xz2_index(gm_ctx* ctx, const double* xmin, const double* ymin, const double* xmax, const double* ymax,
@@ -629,7 +629,7 @@ int gm_xz2_index(gm_ctx* ctx, const double* xmin, const double* ymin, const doub
     else hipLaunchKernelGGL((k_xz2_index<false, false>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, n, g, out, status, ctx->d_err);
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_xz3_index(gm_ctx* ctx, const double* xmin, const double* ymin, const double* zmin, const double* xmax,
@@ -665,7 +665,7 @@ int gm_xz3_index(gm_ctx* ctx, const double* xmin, const double* ymin, const doub
     else hipLaunchKernelGGL((k_xz3_index<false, false>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, zmin, xmax, ymax, zmax, n, g, zhi, out, status, ctx->d_err);
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_xz3_index_key(gm_ctx* ctx, const double* xmin, const double* ymin, const double* xmax, const double* ymax,
@@ -694,7 +694,7 @@ int gm_xz3_index_key(gm_ctx* ctx, const double* xmin, const double* ymin, const 
   }
 #undef GM_XZ3K
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 }  // extern "C"

@@ -696,7 +696,7 @@ extern "C" {
 int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const int16_t* bin_ranges,
                      int n_bin_ranges, const int16_t* bin, const int64_t* z, int64_t n, uint64_t* mask,
                      int64_t* ids, int64_t ids_cap, int64_t* n_match) {
-  if (!ctx || !filter_bytes || n < 0 || n_bin_ranges < 0) return GM_E_INVALID;
+  if (!ctx || !filter_bytes || n < 0 || n_bin_ranges < 0 || (ids && ids_cap < 0)) return GM_E_INVALID;
   std::vector<int32_t> desc;
   if (!build_z3_desc(filter_bytes, filter_len, desc)) {
     set_error("gm_z3filter_scan: malformed Z3Filter bytes");
@@ -740,7 +740,7 @@ int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len
 
 int gm_z2filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const int64_t* z, int64_t n,
                      uint64_t* mask, int64_t* ids, int64_t ids_cap, int64_t* n_match) {
-  if (!ctx || !filter_bytes || n < 0 || filter_len < 4) return GM_E_INVALID;
+  if (!ctx || !filter_bytes || n < 0 || filter_len < 4 || (ids && ids_cap < 0)) return GM_E_INVALID;
   const int32_t nxy = be32(filter_bytes);
   if (nxy < 0 || 4 + (size_t)nxy * 16 > filter_len) {
     set_error("gm_z2filter_scan: malformed Z2Filter bytes");
@@ -818,7 +818,7 @@ static int filter_rows(gm_ctx* ctx, bool z3, const std::vector<int32_t>& desc, c
 int gm_z3filter_scan_rows(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const uint8_t* rows,
                           const int64_t* row_off, int key_offset, int64_t n, uint64_t* mask, int64_t* ids,
                           int64_t ids_cap, int64_t* n_match, int64_t* n_short) {
-  if (!ctx || !filter_bytes || n < 0) return GM_E_INVALID;
+  if (!ctx || !filter_bytes || n < 0 || (ids && ids_cap < 0)) return GM_E_INVALID;
   std::vector<int32_t> desc;
   if (!build_z3_desc(filter_bytes, filter_len, desc)) {
     set_error("gm_z3filter_scan_rows: malformed Z3Filter bytes");
@@ -830,7 +830,7 @@ int gm_z3filter_scan_rows(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filte
 int gm_z2filter_scan_rows(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const uint8_t* rows,
                           const int64_t* row_off, int key_offset, int64_t n, uint64_t* mask, int64_t* ids,
                           int64_t ids_cap, int64_t* n_match, int64_t* n_short) {
-  if (!ctx || !filter_bytes || n < 0 || filter_len < 4) return GM_E_INVALID;
+  if (!ctx || !filter_bytes || n < 0 || filter_len < 4 || (ids && ids_cap < 0)) return GM_E_INVALID;
   const int32_t nxy = be32(filter_bytes);
   if (nxy < 0 || 4 + (size_t)nxy * 16 > filter_len) {
     set_error("gm_z2filter_scan_rows: malformed Z2Filter bytes");
@@ -844,7 +844,7 @@ int gm_z2filter_scan_rows(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filte
 int gm_strict_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t* t_ms, int64_t n, const double* bbox,
                    int has_during, int64_t lo, int64_t hi, uint64_t* mask, int64_t* ids, int64_t ids_cap,
                    int64_t* n_match) {
-  if (!ctx || !bbox || n < 0) return GM_E_INVALID;
+  if (!ctx || !bbox || n < 0 || (ids && ids_cap < 0)) return GM_E_INVALID;
   if (n == 0) { if (n_match) *n_match = 0; return GM_OK; }
   if (!x || !y || (has_during && !t_ms)) return GM_E_INVALID;
   ScanBufs b;

@@ -148,8 +148,9 @@ int take_fault(gm_ctx* ctx, const char* what);
 
 // reset the error summary before a call that reports one
 int begin_summary(gm_ctx* ctx, gm_batch_status* summary);
-// read the summary back (synchronises the stream); maps to GM_OK / per-element semantics
-int end_summary(gm_ctx* ctx, gm_batch_status* summary);
+// read the summary back (synchronises the stream).  GM_E_ELEMENT when an element failed and the
+// caller gave no status[] to find it in; GM_OK otherwise, and always without a summary (asynchronous)
+int end_summary(gm_ctx* ctx, gm_batch_status* summary, const uint8_t* status);
 
 // Resident block count of `kernel` at `block` threads per block on `device`: occupancy x CUs,
 // computed once per (kernel, device) under a lock (contexts on different devices and concurrent

@@ -154,7 +154,7 @@ int gm_legacy_z3_index(gm_ctx* ctx, const double* x, const double* y, const int6
                          t, n, lon, lat, tim, ymax, z, status, ctx->d_err);
   }
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_legacy_z3_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int curve, int period, double* x, double* y,
@@ -181,7 +181,7 @@ int gm_legacy_z2_index(gm_ctx* ctx, const double* x, const double* y, int64_t n,
   hipLaunchKernelGGL(k_legacy_z2_index, dim3(legacy_grid(n)), dim3(LTPB), 0, ctx->stream, x, y, n, lon, lat, lenient,
                      z, status, ctx->d_err);
   GM_CHECK_LAUNCH();
-  return end_summary(ctx, summary);
+  return end_summary(ctx, summary, status);
 }
 
 int gm_legacy_z2_invert(gm_ctx* ctx, const int64_t* z, int64_t n, double* x, double* y) {

@@ -924,7 +924,7 @@ constexpr int64_t P1CAP = LDS_SORT;
 // finish(total, dbuf, dstart, doff): query-order gather of the batch buffer and the copy out
 template <class PerQFn, class LaunchFn, class FinishFn>
 int run_batch(gm_ctx* ctx, int64_t q_base, int64_t nq, int64_t fcap, int64_t rcap, PerQFn& per_query, LaunchFn& launch,
-              int64_t* out_off, int64_t cap, int64_t* needed, int32_t* query_status, FinishFn finish) {
+              int64_t* out_off, int64_t cap, int64_t* needed, int32_t* query_status, bool* failed, FinishFn finish) {
   hipStream_t s = ctx->stream;
   rcap = next_pow2(std::max<int64_t>(rcap, 16));
   size_t free_b = 0, total_b = 0;
@@ -999,6 +999,8 @@ int run_batch(gm_ctx* ctx, int64_t q_base, int64_t nq, int64_t fcap, int64_t rca
       continue;
     }
     if (query_status) memcpy(query_status, stats.data(), (size_t)nq * 4);
+    for (int64_t i = 0; i < nq; ++i)
+      if (stats[(size_t)i] != QS_OK) *failed = true;
     if (needed) *needed = total;
     if (total > cap) return GM_E_CAPACITY;
     return total > 0 ? finish(total, dbuf, (const int64_t*)dstart, (const int64_t*)doff, nq) : GM_OK;
@@ -1009,12 +1011,13 @@ int run_batch(gm_ctx* ctx, int64_t q_base, int64_t nq, int64_t fcap, int64_t rca
 // k's result copy (a second stream) overlaps chunk k + 1's kernels: the copy back of 10^7-10^8
 // ranges costs as much as their computation.  The output is identical either way.
 template <class PerQFn, class LaunchFn>
-int run_ranges(gm_ctx* ctx, int64_t nq, int64_t fcap, int64_t rcap, PerQFn per_query, LaunchFn launch, int64_t* out_off,
-               gm_range* out, int64_t cap, int64_t* needed, int32_t* query_status) {
+int run_ranges_batches(gm_ctx* ctx, int64_t nq, int64_t fcap, int64_t rcap, PerQFn& per_query, LaunchFn& launch,
+                       int64_t* out_off, gm_range* out, int64_t cap, int64_t* needed, int32_t* query_status,
+                       bool* failed) {
   hipStream_t s = ctx->stream;
   int64_t qc = ctx->ranges_chunk > 0 ? ctx->ranges_chunk : (nq < 16384 ? nq : std::max<int64_t>(8192, (nq + 7) / 8));
   if (out && device_memory(out)) {   // device output (ranges consumed on the device): gathered in place
-    return run_batch(ctx, 0, nq, fcap, rcap, per_query, launch, out_off, cap, needed, query_status,
+    return run_batch(ctx, 0, nq, fcap, rcap, per_query, launch, out_off, cap, needed, query_status, failed,
                      [&](int64_t total, const gm_range* dbuf, const int64_t* dstart, const int64_t* doff, int64_t n) -> int {
                        hipLaunchKernelGGL(k_gather_ranges, dim3((unsigned)std::min<int64_t>(n, 65536)), dim3(RTPB), 0, s,
                                           dbuf, dstart, doff, n, out);
@@ -1024,7 +1027,7 @@ int run_ranges(gm_ctx* ctx, int64_t nq, int64_t fcap, int64_t rcap, PerQFn per_q
                      });
   }
   if (qc >= nq || !out || !host_pinned(out)) {   // one batch: gather into scratch, one copy
-    return run_batch(ctx, 0, nq, fcap, rcap, per_query, launch, out_off, cap, needed, query_status,
+    return run_batch(ctx, 0, nq, fcap, rcap, per_query, launch, out_off, cap, needed, query_status, failed,
                      [&](int64_t total, const gm_range* dbuf, const int64_t* dstart, const int64_t* doff, int64_t n) -> int {
                        void* dout = nullptr;   // the range scratch is free again
                        int rc = ctx_workspace(ctx, WS_RANGES, (size_t)total * sizeof(gm_range), &dout);
@@ -1054,7 +1057,7 @@ int run_ranges(gm_ctx* ctx, int64_t nq, int64_t fcap, int64_t rcap, PerQFn per_q
     off_c.assign((size_t)m + 1, 0);
     int64_t tot = 0;
     rc = run_batch(ctx, c0, m, fcap, rcap, per_query, launch, off_c.data(), INT64_MAX / 32, &tot,
-                   query_status ? query_status + c0 : nullptr,
+                   query_status ? query_status + c0 : nullptr, failed,
                    [&](int64_t total, const gm_range* dbuf, const int64_t* dstart, const int64_t* doff, int64_t n) -> int {
                      if (over || base + total > cap) { over = true; return GM_OK; }   // capacity: counting only
                      if (used[k]) GM_HIP(hipStreamWaitEvent(s, ctx->ev_copied[k], 0));   // its last copy is done
@@ -1085,6 +1088,22 @@ int run_ranges(gm_ctx* ctx, int64_t nq, int64_t fcap, int64_t rcap, PerQFn per_q
   if (needed) *needed = base;
   ctx->ranges_hint = std::max(ctx->ranges_hint, std::min(base, cap) / std::max<int64_t>(1, (nq + qc - 1) / qc));
   return base > cap ? GM_E_CAPACITY : GM_OK;
+}
+
+// A query that failed (non-zero status) is reported as GM_E_ELEMENT when the caller gave no
+// query_status to find it in: offsets, ranges and *needed are delivered all the same, and
+// GM_E_CAPACITY (or any other failure) takes precedence.
+template <class PerQFn, class LaunchFn>
+int run_ranges(gm_ctx* ctx, int64_t nq, int64_t fcap, int64_t rcap, PerQFn per_query, LaunchFn launch, int64_t* out_off,
+               gm_range* out, int64_t cap, int64_t* needed, int32_t* query_status) {
+  bool failed = false;
+  const int rc = run_ranges_batches(ctx, nq, fcap, rcap, per_query, launch, out_off, out, cap, needed, query_status,
+                                    &failed);
+  if (rc == GM_OK && failed && !query_status) {
+    set_error("at least one query failed; pass query_status to see which");
+    return GM_E_ELEMENT;
+  }
+  return rc;
 }
 
 inline int stop_of(int max_ranges) { return max_ranges <= 0 ? INT32_MAX : max_ranges; }

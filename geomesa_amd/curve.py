@@ -21,7 +21,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import check, ptr
+from ._lib import ALLOW_ELEMENT as _ELEMENT, check, ptr
 
 
 class IllegalArgumentException(ValueError):
@@ -177,7 +177,7 @@ class BinnedTime:
         s = torch.empty(n, dtype=torch.uint8, device=t.device) if status else None
         st = _summary()
         check(ctx.lib.gm_binned_time(ctx.handle, ptr(t), n, p, ptr(b), ptr(o), ptr(s), ctypes.byref(st)),
-              "gm_binned_time")
+              "gm_binned_time", _ELEMENT)
         if status:
             return b, o, s
         _raise_first(st, "BinnedTime")
@@ -213,7 +213,7 @@ class Z3SFC:
         s = torch.empty(n, dtype=torch.uint8, device=x.device) if status else None
         st = _summary()
         check(ctx.lib.gm_z3_index(ctx.handle, ptr(x), ptr(y), ptr(t), n, self.period, self.precision,
-                                  int(bool(lenient)), ptr(z), ptr(s), ctypes.byref(st)), "gm_z3_index")
+                                  int(bool(lenient)), ptr(z), ptr(s), ctypes.byref(st)), "gm_z3_index", _ELEMENT)
         if status:
             return z, s
         _raise_first(st, "Z3SFC.index")
@@ -232,7 +232,7 @@ class Z3SFC:
         s = torch.empty(n, dtype=torch.uint8, device=x.device) if status else None
         st = _summary()
         check(ctx.lib.gm_z3_index_key(ctx.handle, ptr(x), ptr(y), ptr(t), n, self.period, int(bool(lenient)),
-                                      ptr(b), ptr(z), ptr(s), ctypes.byref(st)), "gm_z3_index_key")
+                                      ptr(b), ptr(z), ptr(s), ctypes.byref(st)), "gm_z3_index_key", _ELEMENT)
         if status:
             return b, z, s
         _raise_first(st, "Z3IndexKeySpace.toIndexKey")
@@ -284,7 +284,7 @@ class Z2SFC:
         s = torch.empty(n, dtype=torch.uint8, device=x.device) if status else None
         st = _summary()
         check(ctx.lib.gm_z2_index(ctx.handle, ptr(x), ptr(y), n, self.precision, int(bool(lenient)), ptr(z),
-                                  ptr(s), ctypes.byref(st)), "gm_z2_index")
+                                  ptr(s), ctypes.byref(st)), "gm_z2_index", _ELEMENT)
         if status:
             return z, s
         _raise_first(st, "Z2SFC.index")
@@ -329,7 +329,7 @@ class XZ2SFC:
         s = torch.empty(n, dtype=torch.uint8, device=out.device) if status else None
         st = _summary()
         check(ctx.lib.gm_xz2_index(ctx.handle, *[ptr(c) for c in cols], n, self.g, int(bool(lenient)), ptr(out),
-                                   ptr(s), ctypes.byref(st)), "gm_xz2_index")
+                                   ptr(s), ctypes.byref(st)), "gm_xz2_index", _ELEMENT)
         if status:
             return out, s
         _raise_first(st, "XZ2SFC.index")
@@ -367,7 +367,7 @@ class XZ3SFC:
         s = torch.empty(n, dtype=torch.uint8, device=out.device) if status else None
         st = _summary()
         check(ctx.lib.gm_xz3_index(ctx.handle, *[ptr(c) for c in cols], n, self.g, self.period,
-                                   int(bool(lenient)), ptr(out), ptr(s), ctypes.byref(st)), "gm_xz3_index")
+                                   int(bool(lenient)), ptr(out), ptr(s), ctypes.byref(st)), "gm_xz3_index", _ELEMENT)
         if status:
             return out, s
         _raise_first(st, "XZ3SFC.index")
@@ -390,7 +390,7 @@ class _LegacyBase:
         s = torch.empty(n, dtype=torch.uint8, device=cols[0].device) if status else None
         st = _summary()
         check(getattr(ctx.lib, fn)(ctx.handle, *[ptr(c) for c in cols], n, *extra, int(bool(lenient)), ptr(z), ptr(s),
-                                   ctypes.byref(st)), fn)
+                                   ctypes.byref(st)), fn, _ELEMENT)
         if status:
             return z, s
         _raise_first(st, what)

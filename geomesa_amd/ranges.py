@@ -74,7 +74,7 @@ def call_raw(fn, args, nq, cap, pinned=False):
         if rc == _lib.GM_E_CAPACITY:
             cap = needed.value + 1024
             continue
-        check(rc, fn.__name__)
+        check(rc, fn.__name__, _lib.ALLOW_ELEMENT)   # qst is always given; _run raises from it
         return out_off, out, qst
 
 

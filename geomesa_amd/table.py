@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from . import filters as F
-from ._lib import check, ptr
+from ._lib import ALLOW_ELEMENT as _ELEMENT, check, ptr
 from .keyspace import Z3IndexKeySpace
 
 _ALL64 = -1  # 0xFFFF... as int64
@@ -408,7 +408,7 @@ class XZ3Table(_KeyTable):
         st = _summary()
         check(ctx.lib.gm_xz3_index_key(ctx.handle, *[ptr(c) for c in self.env], ptr(self.t), n, self.ks.sfc.g,
                                        self.ks.period, int(bool(lenient)), ptr(b), ptr(xz), None, ctypes.byref(st)),
-              "gm_xz3_index_key")
+              "gm_xz3_index_key", _ELEMENT)
         _raise_first(st, "XZ3IndexKeySpace.toIndexKey")
         super().__init__(b, xz, shard, shards)
 

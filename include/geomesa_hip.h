@@ -16,8 +16,15 @@
  *  - Per-element failures mirror the JVM exceptions: an optional device uint8 status[] gets
  *    GM_ST_* per element, and an optional host gm_batch_status receives the error count and
  *    the first failing element, so a shim can throw the same IllegalArgumentException the
- *    Scala code throws on the first bad element.  Passing summary = NULL keeps the call
- *    fully asynchronous on the context's stream.
+ *    Scala code throws on the first bad element.
+ *  - The element-failure rule.  An index call returns GM_E_ELEMENT when summary != NULL,
+ *    status == NULL and at least one element failed.  The summary is still filled, every output
+ *    row is still written, and failed rows get the documented zeros.  With status != NULL the
+ *    return code stays GM_OK: the caller has the codes.  With summary == NULL the call stays
+ *    asynchronous on the context's stream and returns GM_OK: a caller passing neither status nor
+ *    summary has opted out of failure reporting.  A ranges call returns GM_E_ELEMENT when
+ *    query_status == NULL and some query has a non-zero status.  Offsets, ranges and *needed are
+ *    still delivered, and GM_E_CAPACITY takes precedence when both apply.
  *  - Thread safety: one gm_ctx per thread; calls on different contexts are independent.
  *  - Configuration knobs the Scala code reads from system properties
  *    (geomesa.scan.ranges.target, geomesa.scan.ranges.recurse, XZ precision g, ...) are
@@ -40,7 +47,10 @@ extern "C" {
 #define GM_E_INVALID (-1)     /* bad argument (null pointer, bad period/precision, malformed filter) */
 #define GM_E_HIP (-2)         /* HIP runtime failure; see gm_last_error() */
 #define GM_E_CAPACITY (-3)    /* output capacity too small; the needed size is reported */
-#define GM_E_ELEMENT (-4)     /* at least one element failed (only when no status[] and no summary) */
+#define GM_E_ELEMENT (-4)     /* at least one element failed and the caller gave nothing to find it in: an index
+                                 call with summary != NULL and status == NULL, or a ranges call with
+                                 query_status == NULL (the element-failure rule above); every output is
+                                 still written */
 #define GM_E_INDEX (-5)       /* a device-side reference check of a join failed (corrupt or mismatched index,
                                  or a broken internal invariant); the call's output is not valid */
 
@@ -226,9 +236,13 @@ int gm_xz3_ranges(gm_ctx* ctx, int64_t n_queries, const int32_t* win_off, const 
    bin_ranges (host, n_bin_ranges pairs of int16, inclusive) restricts the scan to the query's
    epochs (the bins Z3IndexKeySpace.getRanges scans, Z3IndexKeySpace.scala:161-194);
    n_bin_ranges = 0 scans every bin.
-   Outputs (device, each optional): mask = 1 bit per row (bit i%64 of word i/64, ceil(n/64) words),
-   ids = compacted matching row indices (ids_cap entries, in ascending order).
-   *n_match (host) receives the match count (this call synchronises when n_match != NULL). */
+   Outputs (device, each optional): mask = 1 bit per row (bit i%64 of word i/64, exactly ceil(n/64)
+   words; the bits at and above n of the last word are zero, so a popcount of the mask is the match
+   count), ids = compacted matching row indices (ids_cap entries, in ascending order; no entry past
+   ids_cap is written, and ids != NULL with ids_cap < 0 is GM_E_INVALID).
+   *n_match (host) receives the match count (this call synchronises when n_match != NULL);
+   GM_E_CAPACITY when ids is given and the matches exceed ids_cap.  The same output rules hold for
+   every scan below. */
 int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const int16_t* bin_ranges,
                      int n_bin_ranges, const int16_t* bin, const int64_t* z, int64_t n, uint64_t* mask,
                      int64_t* ids, int64_t ids_cap, int64_t* n_match);
@@ -600,7 +614,9 @@ int gm_z3_histogram(gm_ctx* ctx, const double* x, const double* y, const int64_t
                     int64_t* tally);
 
 /* ------------------------------------------------------------------ synthetic data (bench/tests) */
-/* SplitMix64 keyed by (seed, index): lon U[lon0,lon1), lat U[lat0,lat1), t_ms U[t0,t1) */
+/* SplitMix64 keyed by (seed, index): lon U[lon0,lon1), lat U[lat0,lat1), t_ms U[t0,t1).  Each of x, y and
+   t_ms is optional (NULL = that column is not generated; the others get the same values either way);
+   all three NULL with n > 0 is GM_E_INVALID */
 int gm_gen_points(gm_ctx* ctx, uint64_t seed, int64_t n, int64_t index_base, double lon0, double lon1,
                   double lat0, double lat1, int64_t t0, int64_t t1, double* x, double* y, int64_t* t_ms);
 
