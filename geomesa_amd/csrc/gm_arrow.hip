@@ -356,42 +356,25 @@ void launch_z3_arrow(hipStream_t s, bool vec, ArrowPts g, ArrowTime tc, int64_t 
   if (vec && aligned16(g.c) && n >= 2) {
     const int64_t np = n >> 1;
     const unsigned vg = (unsigned)((np + ATPB * AUNROLL - 1) / (ATPB * AUNROLL));
-    if (tc.ms)
-      hipLaunchKernelGGL((k_z3_key_arrow_v<PERIOD, LENIENT, F32, true, AUNROLL>), dim3(vg), dim3(ATPB), 0, s, g, tc, n,
+    with_flags([&](auto T) {
+      hipLaunchKernelGGL((k_z3_key_arrow_v<PERIOD, LENIENT, F32, T(), AUNROLL>), dim3(vg), dim3(ATPB), 0, s, g, tc, n,
                          lon, lat, tim, (short2*)bin, (lv2*)z, (uchar2*)status, err);
-    else
-      hipLaunchKernelGGL((k_z3_key_arrow_v<PERIOD, LENIENT, F32, false, AUNROLL>), dim3(vg), dim3(ATPB), 0, s, g, tc, n,
-                         lon, lat, tim, (short2*)bin, (lv2*)z, (uchar2*)status, err);
+    }, tc.ms != nullptr);
     return;
   }
-  const unsigned grid = agrid((n + 1) >> 1);
-  if (vec) hipLaunchKernelGGL((k_z3_key_arrow<PERIOD, LENIENT, F32, true>), dim3(grid), dim3(ATPB), 0, s, g, tc, n, lon, lat, tim, bin, z, status, err);
-  else hipLaunchKernelGGL((k_z3_key_arrow<PERIOD, LENIENT, F32, false>), dim3(grid), dim3(ATPB), 0, s, g, tc, n, lon, lat, tim, bin, z, status, err);
-}
-
-template <int PERIOD>
-void launch_z3_arrow_p(hipStream_t s, bool vec, bool lenient, bool f32, ArrowPts g, ArrowTime tc, int64_t n, NDim lon,
-                       NDim lat, NDim tim, int16_t* bin, int64_t* z, uint8_t* status, int64_t* err) {
-  if (lenient) {
-    if (f32) launch_z3_arrow<PERIOD, true, true>(s, vec, g, tc, n, lon, lat, tim, bin, z, status, err);
-    else launch_z3_arrow<PERIOD, true, false>(s, vec, g, tc, n, lon, lat, tim, bin, z, status, err);
-  } else {
-    if (f32) launch_z3_arrow<PERIOD, false, true>(s, vec, g, tc, n, lon, lat, tim, bin, z, status, err);
-    else launch_z3_arrow<PERIOD, false, false>(s, vec, g, tc, n, lon, lat, tim, bin, z, status, err);
-  }
+  with_flags([&](auto V) {
+    hipLaunchKernelGGL((k_z3_key_arrow<PERIOD, LENIENT, F32, V()>), dim3(agrid((n + 1) >> 1)), dim3(ATPB), 0, s, g, tc,
+                       n, lon, lat, tim, bin, z, status, err);
+  }, vec);
 }
 
 template <int DIM, int PERIOD>
 void launch_xz_arrow(hipStream_t s, bool lenient, bool f32, ArrowGeom g, ArrowTime tc, int64_t n, int gp, double zhi,
                      int16_t* bin, int64_t* xz, uint8_t* status, int64_t* err) {
-  const unsigned grid = agrid(n);
-  if (lenient) {
-    if (f32) hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, true, true>), dim3(grid), dim3(ATPB), 0, s, g, tc, n, gp, zhi, bin, xz, status, err);
-    else hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, true, false>), dim3(grid), dim3(ATPB), 0, s, g, tc, n, gp, zhi, bin, xz, status, err);
-  } else {
-    if (f32) hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, false, true>), dim3(grid), dim3(ATPB), 0, s, g, tc, n, gp, zhi, bin, xz, status, err);
-    else hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, false, false>), dim3(grid), dim3(ATPB), 0, s, g, tc, n, gp, zhi, bin, xz, status, err);
-  }
+  with_flags([&](auto L, auto F) {
+    hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, L(), F()>), dim3(agrid(n)), dim3(ATPB), 0, s, g, tc, n, gp, zhi,
+                       bin, xz, status, err);
+  }, lenient, f32);
 }
 
 // the List offsets a geometry type needs, outermost first
@@ -423,24 +406,20 @@ extern "C" {
 int gm_z3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* dtg, int64_t n, int period,
                           int lenient, int16_t* bin, int64_t* z, uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || !valid_period(period)) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!point_col_ok(geom) || !bin || !z) return GM_E_INVALID;
   GM_HIP(hipSetDevice(ctx->device));
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
   const NDim lon = lon_dim(21), lat = lat_dim(21), tim = time_dim(period, 21);
   const ArrowTime tc = to_time(dtg);
-  const bool vec = aligned16(z) && (((uintptr_t)bin & 3u) == 0) && (((uintptr_t)status & 1u) == 0) &&
-                   (!tc.ms || aligned16(tc.ms));
-  const bool f32 = geom->ordinal_bits == 32;
+  const bool vec = aligned16(z) && aligned_to<4>(bin) && aligned_to<2>(status) && aligned16(tc.ms);
   const ArrowPts g = to_pts(geom);
-  hipStream_t s = ctx->stream;
-  switch (period) {
-    case DAY: launch_z3_arrow_p<DAY>(s, vec, lenient, f32, g, tc, n, lon, lat, tim, bin, z, status, ctx->d_err); break;
-    case WEEK: launch_z3_arrow_p<WEEK>(s, vec, lenient, f32, g, tc, n, lon, lat, tim, bin, z, status, ctx->d_err); break;
-    case MONTH: launch_z3_arrow_p<MONTH>(s, vec, lenient, f32, g, tc, n, lon, lat, tim, bin, z, status, ctx->d_err); break;
-    default: launch_z3_arrow_p<YEAR>(s, vec, lenient, f32, g, tc, n, lon, lat, tim, bin, z, status, ctx->d_err); break;
-  }
+  with_period(period, [&](auto P) {
+    with_flags([&](auto L, auto F) {
+      launch_z3_arrow<P(), L(), F()>(ctx->stream, vec, g, tc, n, lon, lat, tim, bin, z, status, ctx->d_err);
+    }, lenient != 0, geom->ordinal_bits == 32);
+  });
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -448,27 +427,17 @@ int gm_z3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time
 int gm_z2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, int lenient, int64_t* z, uint8_t* status,
                           gm_batch_status* summary) {
   if (!ctx || n < 0) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!point_col_ok(geom) || !z) return GM_E_INVALID;
   GM_HIP(hipSetDevice(ctx->device));
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
   const NDim lon = lon_dim(31), lat = lat_dim(31);   // Z2SFC object: 31 bits per dimension
-  const bool vec = aligned16(z) && (((uintptr_t)status & 1u) == 0);
   const ArrowPts g = to_pts(geom);
-  const unsigned grid = agrid((n + 1) >> 1);
-  hipStream_t s = ctx->stream;
-  int64_t* err = ctx->d_err;
-  const bool f32 = geom->ordinal_bits == 32;
-#define GM_Z2A(L, F, V) hipLaunchKernelGGL((k_z2_key_arrow<L, F, V>), dim3(grid), dim3(ATPB), 0, s, g, n, lon, lat, z, status, err)
-  if (lenient) {
-    if (f32) { if (vec) GM_Z2A(true, true, true); else GM_Z2A(true, true, false); }
-    else { if (vec) GM_Z2A(true, false, true); else GM_Z2A(true, false, false); }
-  } else {
-    if (f32) { if (vec) GM_Z2A(false, true, true); else GM_Z2A(false, true, false); }
-    else { if (vec) GM_Z2A(false, false, true); else GM_Z2A(false, false, false); }
-  }
-#undef GM_Z2A
+  with_flags([&](auto L, auto F, auto V) {
+    hipLaunchKernelGGL((k_z2_key_arrow<L(), F(), V()>), dim3(agrid((n + 1) >> 1)), dim3(ATPB), 0, ctx->stream, g, n,
+                       lon, lat, z, status, ctx->d_err);
+  }, lenient != 0, geom->ordinal_bits == 32, aligned16(z) && aligned_to<2>(status));
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -476,7 +445,7 @@ int gm_z2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, in
 static int xz_key_arrow(gm_ctx* ctx, int dim, const gm_geom_column* geom, const gm_time_column* dtg, int64_t n, int g,
                         int period, int lenient, int16_t* bin, int64_t* xz, uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || g < 1 || g > (dim == 2 ? 30 : 20) || (dim == 3 && !valid_period(period))) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!geom_col_ok(geom) || !xz || (dim == 3 && !bin)) return GM_E_INVALID;
   GM_HIP(hipSetDevice(ctx->device));
   int rc = begin_summary(ctx, summary);
@@ -487,15 +456,12 @@ static int xz_key_arrow(gm_ctx* ctx, int dim, const gm_geom_column* geom, const 
   const bool f32 = geom->ordinal_bits == 32;
   hipStream_t s = ctx->stream;
   if (dim == 2) {
-    launch_xz_arrow<2, WEEK>(s, lenient, f32, ag, tc, n, g, 0.0, bin, xz, status, ctx->d_err);
+    launch_xz_arrow<2, GM_WEEK>(s, lenient, f32, ag, tc, n, g, 0.0, bin, xz, status, ctx->d_err);   // the one 2-D period
   } else {
     const double zhi = (double)max_offset(period);
-    switch (period) {
-      case DAY: launch_xz_arrow<3, DAY>(s, lenient, f32, ag, tc, n, g, zhi, bin, xz, status, ctx->d_err); break;
-      case WEEK: launch_xz_arrow<3, WEEK>(s, lenient, f32, ag, tc, n, g, zhi, bin, xz, status, ctx->d_err); break;
-      case MONTH: launch_xz_arrow<3, MONTH>(s, lenient, f32, ag, tc, n, g, zhi, bin, xz, status, ctx->d_err); break;
-      default: launch_xz_arrow<3, YEAR>(s, lenient, f32, ag, tc, n, g, zhi, bin, xz, status, ctx->d_err); break;
-    }
+    with_period(period, [&](auto P) {
+      launch_xz_arrow<3, P()>(s, lenient, f32, ag, tc, n, g, zhi, bin, xz, status, ctx->d_err);
+    });
   }
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
@@ -503,7 +469,7 @@ static int xz_key_arrow(gm_ctx* ctx, int dim, const gm_geom_column* geom, const 
 
 int gm_xz2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, int g, int lenient, int64_t* xz,
                            uint8_t* status, gm_batch_status* summary) {
-  return xz_key_arrow(ctx, 2, geom, nullptr, n, g, WEEK, lenient, nullptr, xz, status, summary);
+  return xz_key_arrow(ctx, 2, geom, nullptr, n, g, GM_WEEK, lenient, nullptr, xz, status, summary);
 }
 
 int gm_xz3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* dtg, int64_t n, int g,
@@ -518,10 +484,9 @@ int gm_arrow_points_to_columns(gm_ctx* ctx, const gm_geom_column* geom, int64_t 
   if (!point_col_ok(geom) || !x || !y) return GM_E_INVALID;
   GM_HIP(hipSetDevice(ctx->device));
   const ArrowPts g = to_pts(geom);
-  if (geom->ordinal_bits == 32)
-    hipLaunchKernelGGL((k_points_soa<true>), dim3(agrid(n)), dim3(ATPB), 0, ctx->stream, g, n, x, y);
-  else
-    hipLaunchKernelGGL((k_points_soa<false>), dim3(agrid(n)), dim3(ATPB), 0, ctx->stream, g, n, x, y);
+  with_flags([&](auto F) {
+    hipLaunchKernelGGL((k_points_soa<F()>), dim3(agrid(n)), dim3(ATPB), 0, ctx->stream, g, n, x, y);
+  }, geom->ordinal_bits == 32);
   GM_CHECK_LAUNCH();
   return GM_OK;
 }

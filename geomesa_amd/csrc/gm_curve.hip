@@ -406,7 +406,8 @@ __global__ __launch_bounds__(XTPB) void k_xz3_index_v(const dv2* __restrict__ xm
 
 // ------------------------------------------------------------------ host-side launchers
 
-// pairs per lane; tuning sweeps build variants with -DGM_UNROLL_INV=... (tools/jx_build.sh, tools/curve_ab.sh).
+// pairs per lane; a tuning sweep builds each variant beside the shipped library with
+// `python -m geomesa_amd.build -DGM_UNROLL_INV=4 --out=<path>` and loads it through GEOMESA_HIP_LIB.
 // The key kernel's LDS bin staging fixes UNROLL_KEY at 4; XZ 1 / 2 / 4 were within noise.
 #ifndef GM_UNROLL_KEY
 #define GM_UNROLL_KEY 4
@@ -439,28 +440,14 @@ template <int PERIOD, bool LENIENT, bool STATUS>
 void launch_key(hipStream_t s, const double* x, const double* y, const int64_t* t, int64_t n, int16_t* bin,
                 int64_t* z, uint8_t* status, NDim lon, NDim lat, NDim tim, int64_t* err, bool vec) {
   if (vec) {
-    unsigned grid = grid_for((n >> 1) > 0 ? (n >> 1) : 1, (int64_t)TPB * UNROLL_KEY);
-    hipLaunchKernelGGL((k_z3_index_key<PERIOD, LENIENT, STATUS, UNROLL_KEY>), dim3(grid), dim3(TPB), 0, s,
-                       (const dv2*)x, (const dv2*)y, (const lv2*)t, n, (short2*)bin, (lv2*)z,
-                       (uchar2*)status, lon, lat, tim, err);
+    hipLaunchKernelGGL((k_z3_index_key<PERIOD, LENIENT, STATUS, UNROLL_KEY>),
+                       dim3(pair_grid(n, (int64_t)TPB * UNROLL_KEY)), dim3(TPB), 0, s, (const dv2*)x, (const dv2*)y,
+                       (const lv2*)t, n, (short2*)bin, (lv2*)z, (uchar2*)status, lon, lat, tim, err);
   } else {
     hipLaunchKernelGGL((k_z3_index_key_s<PERIOD, LENIENT, STATUS>), dim3(stride_grid(n)), dim3(TPB), 0, s, x, y, t,
                        n, bin, z, status, lon, lat, tim, err);
   }
 }
-
-template <int PERIOD>
-void launch_key_p(hipStream_t s, const double* x, const double* y, const int64_t* t, int64_t n, int16_t* bin,
-                  int64_t* z, uint8_t* status, NDim lon, NDim lat, NDim tim, int64_t* err, bool lenient, bool vec) {
-  if (lenient) {
-    if (status) launch_key<PERIOD, true, true>(s, x, y, t, n, bin, z, status, lon, lat, tim, err, vec);
-    else launch_key<PERIOD, true, false>(s, x, y, t, n, bin, z, status, lon, lat, tim, err, vec);
-  } else {
-    if (status) launch_key<PERIOD, false, true>(s, x, y, t, n, bin, z, status, lon, lat, tim, err, vec);
-    else launch_key<PERIOD, false, false>(s, x, y, t, n, bin, z, status, lon, lat, tim, err, vec);
-  }
-}
-
 
 }  // namespace gm
 
@@ -471,19 +458,18 @@ extern "C" {
 int gm_z3_index_key(gm_ctx* ctx, const double* x, const double* y, const int64_t* t_ms, int64_t n, int period,
                     int lenient, int16_t* bin, int64_t* z, uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || !valid_period(period)) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!x || !y || !t_ms || !bin || !z) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
   const NDim lon = lon_dim(21), lat = lat_dim(21), tim = time_dim(period, 21);
-  const bool vec = aligned16(x) && aligned16(y) && aligned16(t_ms) && aligned16(z) &&
-                   (((uintptr_t)bin & 3u) == 0) && (((uintptr_t)status & 1u) == 0);
-  switch (period) {
-    case DAY: launch_key_p<DAY>(ctx->stream, x, y, t_ms, n, bin, z, status, lon, lat, tim, ctx->d_err, lenient, vec); break;
-    case WEEK: launch_key_p<WEEK>(ctx->stream, x, y, t_ms, n, bin, z, status, lon, lat, tim, ctx->d_err, lenient, vec); break;
-    case MONTH: launch_key_p<MONTH>(ctx->stream, x, y, t_ms, n, bin, z, status, lon, lat, tim, ctx->d_err, lenient, vec); break;
-    default: launch_key_p<YEAR>(ctx->stream, x, y, t_ms, n, bin, z, status, lon, lat, tim, ctx->d_err, lenient, vec); break;
-  }
+  const bool vec = aligned16(x) && aligned16(y) && aligned16(t_ms) && aligned16(z) && aligned_to<4>(bin) &&
+                   aligned_to<2>(status);
+  with_period(period, [&](auto P) {
+    with_flags([&](auto L, auto S) {
+      launch_key<P(), L(), S()>(ctx->stream, x, y, t_ms, n, bin, z, status, lon, lat, tim, ctx->d_err, vec);
+    }, lenient != 0, status != nullptr);
+  });
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -491,19 +477,15 @@ int gm_z3_index_key(gm_ctx* ctx, const double* x, const double* y, const int64_t
 int gm_z3_index(gm_ctx* ctx, const double* x, const double* y, const int64_t* t, int64_t n, int period,
                 int precision, int lenient, int64_t* z, uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || !valid_period(period) || precision < 1 || precision > 21) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!x || !y || !t || !z) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision), tim = time_dim(period, precision);
-  const unsigned grid = stride_grid(n);
-  if (lenient) {
-    if (status) hipLaunchKernelGGL((k_z3_index<true, true>), dim3(grid), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status, lon, lat, tim, ctx->d_err);
-    else hipLaunchKernelGGL((k_z3_index<true, false>), dim3(grid), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status, lon, lat, tim, ctx->d_err);
-  } else {
-    if (status) hipLaunchKernelGGL((k_z3_index<false, true>), dim3(grid), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status, lon, lat, tim, ctx->d_err);
-    else hipLaunchKernelGGL((k_z3_index<false, false>), dim3(grid), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status, lon, lat, tim, ctx->d_err);
-  }
+  with_flags([&](auto L, auto S) {
+    hipLaunchKernelGGL((k_z3_index<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status,
+                       lon, lat, tim, ctx->d_err);
+  }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -515,9 +497,8 @@ int gm_z3_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int period, int preci
   if (!z || !x || !y || !t) return GM_E_INVALID;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision), tim = time_dim(period, precision);
   if (aligned16(z) && aligned16(x) && aligned16(y) && aligned16(t)) {
-    unsigned grid = grid_for((n >> 1) > 0 ? (n >> 1) : 1, (int64_t)TPB * UNROLL_INV);
-    hipLaunchKernelGGL((k_z3_invert<UNROLL_INV>), dim3(grid), dim3(TPB), 0, ctx->stream, (const lv2*)z, n,
-                       (dv2*)x, (dv2*)y, (lv2*)t, lon, lat, tim);
+    hipLaunchKernelGGL((k_z3_invert<UNROLL_INV>), dim3(pair_grid(n, (int64_t)TPB * UNROLL_INV)), dim3(TPB), 0,
+                       ctx->stream, (const lv2*)z, n, (dv2*)x, (dv2*)y, (lv2*)t, lon, lat, tim);
   } else {
     hipLaunchKernelGGL(k_z3_invert_s, dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, z, n, x, y, t, lon, lat, tim);
   }
@@ -528,34 +509,23 @@ int gm_z3_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int period, int preci
 int gm_z2_index(gm_ctx* ctx, const double* x, const double* y, int64_t n, int precision, int lenient, int64_t* z,
                 uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || precision < 1 || precision > 31) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!x || !y || !z) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision);
-  const bool vec = aligned16(x) && aligned16(y) && aligned16(z) && (((uintptr_t)status & 1u) == 0);
+  const bool vec = aligned16(x) && aligned16(y) && aligned16(z) && aligned_to<2>(status);
   hipStream_t s = ctx->stream;
-  if (vec) {
-    unsigned grid = grid_for((n >> 1) > 0 ? (n >> 1) : 1, (int64_t)TPB * UNROLL_Z2);
-    const dv2* x2 = (const dv2*)x; const dv2* y2 = (const dv2*)y;
-    lv2* z2 = (lv2*)z; uchar2* s2 = (uchar2*)status;
-    if (lenient) {
-      if (status) hipLaunchKernelGGL((k_z2_index<true, true, UNROLL_Z2>), dim3(grid), dim3(TPB), 0, s, x2, y2, n, z2, s2, lon, lat, ctx->d_err);
-      else hipLaunchKernelGGL((k_z2_index<true, false, UNROLL_Z2>), dim3(grid), dim3(TPB), 0, s, x2, y2, n, z2, s2, lon, lat, ctx->d_err);
-    } else {
-      if (status) hipLaunchKernelGGL((k_z2_index<false, true, UNROLL_Z2>), dim3(grid), dim3(TPB), 0, s, x2, y2, n, z2, s2, lon, lat, ctx->d_err);
-      else hipLaunchKernelGGL((k_z2_index<false, false, UNROLL_Z2>), dim3(grid), dim3(TPB), 0, s, x2, y2, n, z2, s2, lon, lat, ctx->d_err);
-    }
-  } else {
-    unsigned grid = stride_grid(n);
-    if (lenient) {
-      if (status) hipLaunchKernelGGL((k_z2_index_s<true, true>), dim3(grid), dim3(TPB), 0, s, x, y, n, z, status, lon, lat, ctx->d_err);
-      else hipLaunchKernelGGL((k_z2_index_s<true, false>), dim3(grid), dim3(TPB), 0, s, x, y, n, z, status, lon, lat, ctx->d_err);
-    } else {
-      if (status) hipLaunchKernelGGL((k_z2_index_s<false, true>), dim3(grid), dim3(TPB), 0, s, x, y, n, z, status, lon, lat, ctx->d_err);
-      else hipLaunchKernelGGL((k_z2_index_s<false, false>), dim3(grid), dim3(TPB), 0, s, x, y, n, z, status, lon, lat, ctx->d_err);
-    }
-  }
+  if (vec)
+    with_flags([&](auto L, auto S) {
+      hipLaunchKernelGGL((k_z2_index<L(), S(), UNROLL_Z2>), dim3(pair_grid(n, (int64_t)TPB * UNROLL_Z2)), dim3(TPB), 0,
+                         s, (const dv2*)x, (const dv2*)y, n, (lv2*)z, (uchar2*)status, lon, lat, ctx->d_err);
+    }, lenient != 0, status != nullptr);
+  else
+    with_flags([&](auto L, auto S) {
+      hipLaunchKernelGGL((k_z2_index_s<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, s, x, y, n, z, status, lon, lat,
+                         ctx->d_err);
+    }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -566,9 +536,8 @@ int gm_z2_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int precision, double
   if (!z || !x || !y) return GM_E_INVALID;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision);
   if (aligned16(z) && aligned16(x) && aligned16(y)) {
-    unsigned grid = grid_for((n >> 1) > 0 ? (n >> 1) : 1, (int64_t)TPB * UNROLL_INV2);
-    hipLaunchKernelGGL((k_z2_invert<UNROLL_INV2>), dim3(grid), dim3(TPB), 0, ctx->stream, (const lv2*)z, n,
-                       (dv2*)x, (dv2*)y, lon, lat);
+    hipLaunchKernelGGL((k_z2_invert<UNROLL_INV2>), dim3(pair_grid(n, (int64_t)TPB * UNROLL_INV2)), dim3(TPB), 0,
+                       ctx->stream, (const lv2*)z, n, (dv2*)x, (dv2*)y, lon, lat);
   } else {
     hipLaunchKernelGGL(k_z2_invert_s, dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, z, n, x, y, lon, lat);
   }
@@ -579,22 +548,16 @@ int gm_z2_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int precision, double
 int gm_binned_time(gm_ctx* ctx, const int64_t* t_ms, int64_t n, int period, int16_t* bin, int64_t* offset,
                    uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || !valid_period(period)) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!t_ms || !bin || !offset) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
-  const unsigned grid = stride_grid(n);
-  hipStream_t s = ctx->stream;
-#define GM_BT(P)                                                                                          \
-  if (status) hipLaunchKernelGGL((k_binned_time<P, true>), dim3(grid), dim3(TPB), 0, s, t_ms, n, bin, offset, status, ctx->d_err); \
-  else hipLaunchKernelGGL((k_binned_time<P, false>), dim3(grid), dim3(TPB), 0, s, t_ms, n, bin, offset, status, ctx->d_err);
-  switch (period) {
-    case DAY: GM_BT(DAY) break;
-    case WEEK: GM_BT(WEEK) break;
-    case MONTH: GM_BT(MONTH) break;
-    default: GM_BT(YEAR) break;
-  }
-#undef GM_BT
+  with_period(period, [&](auto P) {
+    with_flags([&](auto S) {
+      hipLaunchKernelGGL((k_binned_time<P(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, t_ms, n, bin,
+                         offset, status, ctx->d_err);
+    }, status != nullptr);
+  });
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -602,32 +565,24 @@ int gm_binned_time(gm_ctx* ctx, const int64_t* t_ms, int64_t n, int period, int1
 int gm_xz2_index(gm_ctx* ctx, const double* xmin, const double* ymin, const double* xmax, const double* ymax,
                  int64_t n, int g, int lenient, int64_t* out, uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || g < 1 || g > 30) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!xmin || !ymin || !xmax || !ymax || !out) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
-  const unsigned grid = stride_grid(n);
   hipStream_t s = ctx->stream;
-  if (aligned16(xmin) && aligned16(ymin) && aligned16(xmax) && aligned16(ymax) && aligned16(out) &&
-      (((uintptr_t)status & 1u) == 0)) {
-    const unsigned vg = grid_for((n >> 1) > 0 ? (n >> 1) : 1, (int64_t)XTPB * UNROLL_XZ);
-    const dv2 *a = (const dv2*)xmin, *b = (const dv2*)ymin, *c = (const dv2*)xmax, *d = (const dv2*)ymax;
-    lv2* o = (lv2*)out;
-    uchar2* st = (uchar2*)status;
-    if (lenient) {
-      if (status) hipLaunchKernelGGL((k_xz2_index_v<true, true, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, n, g, o, st, ctx->d_err);
-      else hipLaunchKernelGGL((k_xz2_index_v<true, false, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, n, g, o, st, ctx->d_err);
-    } else {
-      if (status) hipLaunchKernelGGL((k_xz2_index_v<false, true, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, n, g, o, st, ctx->d_err);
-      else hipLaunchKernelGGL((k_xz2_index_v<false, false, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, n, g, o, st, ctx->d_err);
-    }
-  } else if (lenient) {
-    if (status) hipLaunchKernelGGL((k_xz2_index<true, true>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, n, g, out, status, ctx->d_err);
-    else hipLaunchKernelGGL((k_xz2_index<true, false>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, n, g, out, status, ctx->d_err);
-  } else {
-    if (status) hipLaunchKernelGGL((k_xz2_index<false, true>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, n, g, out, status, ctx->d_err);
-    else hipLaunchKernelGGL((k_xz2_index<false, false>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, n, g, out, status, ctx->d_err);
-  }
+  const bool vec = aligned16(xmin) && aligned16(ymin) && aligned16(xmax) && aligned16(ymax) && aligned16(out) &&
+                   aligned_to<2>(status);
+  if (vec)
+    with_flags([&](auto L, auto S) {
+      hipLaunchKernelGGL((k_xz2_index_v<L(), S(), UNROLL_XZ>), dim3(pair_grid(n, (int64_t)XTPB * UNROLL_XZ)),
+                         dim3(XTPB), 0, s, (const dv2*)xmin, (const dv2*)ymin, (const dv2*)xmax, (const dv2*)ymax, n, g,
+                         (lv2*)out, (uchar2*)status, ctx->d_err);
+    }, lenient != 0, status != nullptr);
+  else
+    with_flags([&](auto L, auto S) {
+      hipLaunchKernelGGL((k_xz2_index<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, n, g,
+                         out, status, ctx->d_err);
+    }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -636,34 +591,25 @@ int gm_xz3_index(gm_ctx* ctx, const double* xmin, const double* ymin, const doub
                  const double* ymax, const double* zmax, int64_t n, int g, int period, int lenient, int64_t* out,
                  uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || g < 1 || g > 20 || !valid_period(period)) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!xmin || !ymin || !zmin || !xmax || !ymax || !zmax || !out) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
-  const unsigned grid = stride_grid(n);
   const double zhi = (double)max_offset(period);
   hipStream_t s = ctx->stream;
-  if (aligned16(xmin) && aligned16(ymin) && aligned16(zmin) && aligned16(xmax) && aligned16(ymax) &&
-      aligned16(zmax) && aligned16(out) && (((uintptr_t)status & 1u) == 0)) {
-    const unsigned vg = grid_for((n >> 1) > 0 ? (n >> 1) : 1, (int64_t)XTPB * UNROLL_XZ);
-    const dv2 *a = (const dv2*)xmin, *b = (const dv2*)ymin, *c = (const dv2*)zmin;
-    const dv2 *d = (const dv2*)xmax, *e = (const dv2*)ymax, *f = (const dv2*)zmax;
-    lv2* o = (lv2*)out;
-    uchar2* st = (uchar2*)status;
-    if (lenient) {
-      if (status) hipLaunchKernelGGL((k_xz3_index_v<true, true, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, e, f, n, g, zhi, o, st, ctx->d_err);
-      else hipLaunchKernelGGL((k_xz3_index_v<true, false, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, e, f, n, g, zhi, o, st, ctx->d_err);
-    } else {
-      if (status) hipLaunchKernelGGL((k_xz3_index_v<false, true, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, e, f, n, g, zhi, o, st, ctx->d_err);
-      else hipLaunchKernelGGL((k_xz3_index_v<false, false, UNROLL_XZ>), dim3(vg), dim3(XTPB), 0, s, a, b, c, d, e, f, n, g, zhi, o, st, ctx->d_err);
-    }
-  } else if (lenient) {
-    if (status) hipLaunchKernelGGL((k_xz3_index<true, true>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, zmin, xmax, ymax, zmax, n, g, zhi, out, status, ctx->d_err);
-    else hipLaunchKernelGGL((k_xz3_index<true, false>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, zmin, xmax, ymax, zmax, n, g, zhi, out, status, ctx->d_err);
-  } else {
-    if (status) hipLaunchKernelGGL((k_xz3_index<false, true>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, zmin, xmax, ymax, zmax, n, g, zhi, out, status, ctx->d_err);
-    else hipLaunchKernelGGL((k_xz3_index<false, false>), dim3(grid), dim3(TPB), 0, s, xmin, ymin, zmin, xmax, ymax, zmax, n, g, zhi, out, status, ctx->d_err);
-  }
+  const bool vec = aligned16(xmin) && aligned16(ymin) && aligned16(zmin) && aligned16(xmax) && aligned16(ymax) &&
+                   aligned16(zmax) && aligned16(out) && aligned_to<2>(status);
+  if (vec)
+    with_flags([&](auto L, auto S) {
+      hipLaunchKernelGGL((k_xz3_index_v<L(), S(), UNROLL_XZ>), dim3(pair_grid(n, (int64_t)XTPB * UNROLL_XZ)),
+                         dim3(XTPB), 0, s, (const dv2*)xmin, (const dv2*)ymin, (const dv2*)zmin, (const dv2*)xmax,
+                         (const dv2*)ymax, (const dv2*)zmax, n, g, zhi, (lv2*)out, (uchar2*)status, ctx->d_err);
+    }, lenient != 0, status != nullptr);
+  else
+    with_flags([&](auto L, auto S) {
+      hipLaunchKernelGGL((k_xz3_index<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, s, xmin, ymin, zmin, xmax, ymax,
+                         zmax, n, g, zhi, out, status, ctx->d_err);
+    }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -672,27 +618,17 @@ int gm_xz3_index_key(gm_ctx* ctx, const double* xmin, const double* ymin, const 
                      const int64_t* t_ms, int64_t n, int g, int period, int lenient, int16_t* bin, int64_t* xz,
                      uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || g < 1 || g > 20 || !valid_period(period)) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!xmin || !ymin || !xmax || !ymax || !bin || !xz) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
-  const unsigned grid = stride_grid(n);
   const double zhi = (double)max_offset(period);
-  hipStream_t s = ctx->stream;
-#define GM_XZ3K(P)                                                                                                   \
-  do {                                                                                                               \
-    auto k = lenient ? (status ? k_xz3_index_key<P, true, true> : k_xz3_index_key<P, true, false>)                  \
-                     : (status ? k_xz3_index_key<P, false, true> : k_xz3_index_key<P, false, false>);               \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, t_ms, n, g, zhi, bin, xz, status,     \
-                       ctx->d_err);                                                                                  \
-  } while (0)
-  switch (period) {
-    case GM_DAY: GM_XZ3K(GM_DAY); break;
-    case GM_WEEK: GM_XZ3K(GM_WEEK); break;
-    case GM_MONTH: GM_XZ3K(GM_MONTH); break;
-    default: GM_XZ3K(GM_YEAR); break;
-  }
-#undef GM_XZ3K
+  with_period(period, [&](auto P) {
+    with_flags([&](auto L, auto S) {
+      hipLaunchKernelGGL((k_xz3_index_key<P(), L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, xmin, ymin,
+                         xmax, ymax, t_ms, n, g, zhi, bin, xz, status, ctx->d_err);
+    }, lenient != 0, status != nullptr);
+  });
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }

@@ -631,6 +631,23 @@ static bool build_z3_desc(const uint8_t* b, size_t len, std::vector<int32_t>& d)
   return true;
 }
 
+// Z2Filter's bytes (a count, then xmin, ymin, xmax, ymax per box, big-endian) -> the boxes' 4 nxy words
+static bool build_z2_desc(const uint8_t* b, size_t len, std::vector<int32_t>& xy) {
+  if (len < 4) return false;
+  const int32_t nxy = be32(b);
+  if (nxy < 0 || 4 + (size_t)nxy * 16 > len) return false;
+  xy.resize((size_t)nxy * 4);
+  for (size_t i = 0; i < xy.size(); ++i) xy[i] = be32(b + 4 + 4 * i);
+  return true;
+}
+
+// a scan's descriptor, from pageable host memory to b.desc: the copy is waited for
+static int upload_desc(gm_ctx* ctx, const ScanBufs& b, const int32_t* words, size_t count) {
+  GM_HIP(hipMemcpyAsync(b.desc, words, count * 4, hipMemcpyHostToDevice, ctx->stream));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  return GM_OK;
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -715,41 +732,35 @@ int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len
   ScanBufs b;
   int rc = alloc_scan(ctx, n, mask, buf.size(), b);
   if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(b.desc, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  GM_HIP(hipStreamSynchronize(ctx->stream));  // buf is pageable host memory
+  if ((rc = upload_desc(ctx, b, buf.data(), buf.size()))) return rc;
   const uint64_t* d_dil = (const uint64_t*)b.desc;
   const int32_t* d_desc = b.desc + 2 * dil.size();
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
   const size_t lds = desc.size() * 4;
-  const bool fast = desc[0] <= FBOX && n_bin_ranges <= FBIN;
-  if (aligned16(bin) && aligned16(z) && fast)
-    hipLaunchKernelGGL(k_z3filter_mask_v<true>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const sv2*)bin,
-                       (const lv2*)z, n, d_dil, d_desc, d_desc + fwords, n_bin_ranges, b.mask, b.counts);
-  else if (aligned16(bin) && aligned16(z))
-    hipLaunchKernelGGL(k_z3filter_mask_v<false>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const sv2*)bin,
-                       (const lv2*)z, n, d_dil, d_desc, d_desc + fwords, n_bin_ranges, b.mask, b.counts);
+  if (aligned16(bin) && aligned16(z))
+    with_flags([&](auto FAST) {
+      hipLaunchKernelGGL(k_z3filter_mask_v<FAST()>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream,
+                         (const sv2*)bin, (const lv2*)z, n, d_dil, d_desc, d_desc + fwords, n_bin_ranges, b.mask,
+                         b.counts);
+    }, desc[0] <= FBOX && n_bin_ranges <= FBIN);
   else
     hipLaunchKernelGGL(k_z3filter_mask, dim3((unsigned)nblocks), dim3(FTPB), lds, ctx->stream, bin, z, n, d_desc,
                        fwords, d_desc + fwords, n_bin_ranges, b.mask, b.counts);
   GM_CHECK_LAUNCH();
-  rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  if (rc) return rc;
-  if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
-  return GM_OK;
+  return end_scan(ctx, n, b, ids, ids_cap, n_match);
 }
 
 int gm_z2filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const int64_t* z, int64_t n,
                      uint64_t* mask, int64_t* ids, int64_t ids_cap, int64_t* n_match) {
   if (!ctx || !filter_bytes || n < 0 || filter_len < 4 || (ids && ids_cap < 0)) return GM_E_INVALID;
-  const int32_t nxy = be32(filter_bytes);
-  if (nxy < 0 || 4 + (size_t)nxy * 16 > filter_len) {
+  std::vector<int32_t> xy;
+  if (!build_z2_desc(filter_bytes, filter_len, xy)) {
     set_error("gm_z2filter_scan: malformed Z2Filter bytes");
     return GM_E_INVALID;
   }
   if (n == 0) { if (n_match) *n_match = 0; return GM_OK; }
   if (!z) return GM_E_INVALID;
-  std::vector<int32_t> xy((size_t)nxy * 4);
-  for (size_t i = 0; i < xy.size(); ++i) xy[i] = be32(filter_bytes + 4 + 4 * i);
+  const int nxy = (int)(xy.size() / 4);
   // device layout: [dilated boxes u64 x 4 nxy][boxes int32 x 4 nxy]
   std::vector<uint64_t> dil;
   z2_dilated_boxes(xy.data(), nxy, dil);
@@ -759,25 +770,20 @@ int gm_z2filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len
   ScanBufs b;
   int rc = alloc_scan(ctx, n, mask, buf.size(), b);
   if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(b.desc, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  GM_HIP(hipStreamSynchronize(ctx->stream));
+  if ((rc = upload_desc(ctx, b, buf.data(), buf.size()))) return rc;
   const uint64_t* d_dil = (const uint64_t*)b.desc;
   const int32_t* d_xy = b.desc + 2 * dil.size();
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
-  if (aligned16(z) && nxy <= FBOX)
-    hipLaunchKernelGGL(k_z2filter_mask_v<true>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const lv2*)z, n,
-                       d_dil, d_xy, nxy, b.mask, b.counts);
-  else if (aligned16(z))
-    hipLaunchKernelGGL(k_z2filter_mask_v<false>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const lv2*)z, n,
-                       d_dil, d_xy, nxy, b.mask, b.counts);
+  if (aligned16(z))
+    with_flags([&](auto FAST) {
+      hipLaunchKernelGGL(k_z2filter_mask_v<FAST()>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const lv2*)z,
+                         n, d_dil, d_xy, nxy, b.mask, b.counts);
+    }, nxy <= FBOX);
   else
     hipLaunchKernelGGL(k_z2filter_mask, dim3((unsigned)nblocks), dim3(FTPB), xy.size() * 4 + 4, ctx->stream, z, n,
                        d_xy, nxy, b.mask, b.counts);
   GM_CHECK_LAUNCH();
-  rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  if (rc) return rc;
-  if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
-  return GM_OK;
+  return end_scan(ctx, n, b, ids, ids_cap, n_match);
 }
 
 // shared driver of gm_z3filter_scan_rows / gm_z2filter_scan_rows
@@ -792,27 +798,23 @@ static int filter_rows(gm_ctx* ctx, bool z3, const std::vector<int32_t>& desc, c
   int rc = alloc_scan(ctx, n, mask, dw + 4, b);
   if (rc) return rc;
   unsigned long long* d_short = (unsigned long long*)(b.desc + dw);
-  GM_HIP(hipMemcpyAsync(b.desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   GM_HIP(hipMemsetAsync(d_short, 0, 8, ctx->stream));
-  GM_HIP(hipStreamSynchronize(ctx->stream));  // desc is pageable host memory
+  if ((rc = upload_desc(ctx, b, desc.data(), desc.size()))) return rc;
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
   const size_t lds = std::max<size_t>(desc.size() * 4, 4);
-  if (z3)
-    hipLaunchKernelGGL(k_filter_rows_mask<true>, dim3((unsigned)nblocks), dim3(FTPB), lds, ctx->stream, rows, row_off,
+  with_flags([&](auto Z3) {
+    hipLaunchKernelGGL(k_filter_rows_mask<Z3()>, dim3((unsigned)nblocks), dim3(FTPB), lds, ctx->stream, rows, row_off,
                        key_offset, n, b.desc, (int)desc.size(), b.mask, b.counts, d_short);
-  else
-    hipLaunchKernelGGL(k_filter_rows_mask<false>, dim3((unsigned)nblocks), dim3(FTPB), lds, ctx->stream, rows, row_off,
-                       key_offset, n, b.desc, (int)desc.size(), b.mask, b.counts, d_short);
+  }, z3);
   GM_CHECK_LAUNCH();
-  rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  if (rc) return rc;
-  if (n_short) {
+  // the short-row count is read back before the capacity is answered
+  return end_scan(ctx, n, b, ids, ids_cap, n_match, [&]() -> int {
+    if (!n_short) return GM_OK;
     GM_HIP(hipMemcpyAsync(ctx->h_pinned, d_short, 8, hipMemcpyDeviceToHost, ctx->stream));
     GM_HIP(hipStreamSynchronize(ctx->stream));
     *n_short = ctx->h_pinned[0];
-  }
-  if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
-  return GM_OK;
+    return GM_OK;
+  });
 }
 
 int gm_z3filter_scan_rows(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const uint8_t* rows,
@@ -831,13 +833,11 @@ int gm_z2filter_scan_rows(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filte
                           const int64_t* row_off, int key_offset, int64_t n, uint64_t* mask, int64_t* ids,
                           int64_t ids_cap, int64_t* n_match, int64_t* n_short) {
   if (!ctx || !filter_bytes || n < 0 || filter_len < 4 || (ids && ids_cap < 0)) return GM_E_INVALID;
-  const int32_t nxy = be32(filter_bytes);
-  if (nxy < 0 || 4 + (size_t)nxy * 16 > filter_len) {
+  std::vector<int32_t> xy;
+  if (!build_z2_desc(filter_bytes, filter_len, xy)) {
     set_error("gm_z2filter_scan_rows: malformed Z2Filter bytes");
     return GM_E_INVALID;
   }
-  std::vector<int32_t> xy((size_t)nxy * 4);
-  for (size_t i = 0; i < xy.size(); ++i) xy[i] = be32(filter_bytes + 4 + 4 * i);
   return filter_rows(ctx, false, xy, rows, row_off, key_offset, n, mask, ids, ids_cap, n_match, n_short);
 }
 
@@ -851,28 +851,20 @@ int gm_strict_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t*
   int rc = alloc_scan(ctx, n, mask, 0, b);
   if (rc) return rc;
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
-  if (aligned16(x) && aligned16(y) && (!has_during || aligned16(t_ms))) {
-    const dv2* x2 = (const dv2*)x;
-    const dv2* y2 = (const dv2*)y;
-    const lv2* t2 = (const lv2*)t_ms;
-    uint64_t* m8 = b.mask;
-    if (has_during)
-      hipLaunchKernelGGL((k_strict_mask_v<true>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, x2, y2, t2, n,
-                         bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, m8, b.counts);
-    else
-      hipLaunchKernelGGL((k_strict_mask_v<false>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, x2, y2, t2, n,
-                         bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, m8, b.counts);
-  } else if (has_during)
-    hipLaunchKernelGGL((k_strict_mask<true>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, x, y, t_ms, n,
-                       bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask, b.counts);
+  const bool vec = aligned16(x) && aligned16(y) && (!has_during || aligned16(t_ms));
+  if (vec)
+    with_flags([&](auto D) {
+      hipLaunchKernelGGL((k_strict_mask_v<D()>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const dv2*)x,
+                         (const dv2*)y, (const lv2*)t_ms, n, bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask,
+                         b.counts);
+    }, has_during != 0);
   else
-    hipLaunchKernelGGL((k_strict_mask<false>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, x, y, t_ms, n,
-                       bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask, b.counts);
+    with_flags([&](auto D) {
+      hipLaunchKernelGGL((k_strict_mask<D()>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, x, y, t_ms, n,
+                         bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask, b.counts);
+    }, has_during != 0);
   GM_CHECK_LAUNCH();
-  rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  if (rc) return rc;
-  if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
-  return GM_OK;
+  return end_scan(ctx, n, b, ids, ids_cap, n_match);
 }
 
 int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
@@ -898,12 +890,11 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
     rf = RF_Z3;
   } else if (f->z2filter) {
     if (f->z2filter_len < 4) return GM_E_INVALID;
-    nxy = be32(f->z2filter);
-    if (nxy < 0 || 4 + (size_t)nxy * 16 > f->z2filter_len) {
+    if (!build_z2_desc(f->z2filter, f->z2filter_len, desc)) {
       set_error("gm_table_scan: malformed Z2Filter bytes");
       return GM_E_INVALID;
     }
-    for (int i = 0; i < 4 * nxy; ++i) desc.push_back(be32(f->z2filter + 4 + 4 * i));
+    nxy = (int)(desc.size() / 4);
     rf = RF_Z2;
   }
   // the BatchScanner's view of the ranges: sorted, overlapping / adjacent ones merged
@@ -965,23 +956,18 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
     ScanBufs b;
     rc = alloc_scan(ctx, total, nullptr, buf.size() + 4, b);
     if (rc) return rc;
-    if (!buf.empty()) {
-      GM_HIP(hipMemcpyAsync(b.desc, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, s));
-      GM_HIP(hipStreamSynchronize(s));
-    }
+    if (!buf.empty() && (rc = upload_desc(ctx, b, buf.data(), buf.size()))) return rc;
     FullFilter ff{f->xmin, f->ymin, f->xmax, f->ymax, f->t_ms, env ? (const double*)b.desc : nullptr, f->n_boxes,
                   f->t_lo, f->t_hi, f->rows ? f->rows : perm};
     const int32_t* d_desc = b.desc + box_words;
     const int64_t nblocks = (total + FROWS - 1) / FROWS;
-    void (*kern)(const uint16_t*, const uint64_t*, const int64_t*, const int64_t*, int64_t, int64_t, const int32_t*,
-                 int, FullFilter, uint64_t*, int32_t*) = nullptr;
-#define GM_RANGE_MASK(R)                                                                   \
-  (env ? (dur ? k_range_mask<R, true, true> : k_range_mask<R, true, false>)               \
-       : (dur ? k_range_mask<R, false, true> : k_range_mask<R, false, false>))
-    kern = rf == RF_Z3 ? GM_RANGE_MASK(RF_Z3) : rf == RF_Z2 ? GM_RANGE_MASK(RF_Z2) : GM_RANGE_MASK(RF_NONE);
-#undef GM_RANGE_MASK
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(FTPB), 0, s, (const uint16_t*)bin, (const uint64_t*)z, coff,
-                       start, nr, total, d_desc, nxy, ff, b.mask, b.counts);
+    with_value<RF_Z3, RF_Z2, RF_NONE>(rf, [&](auto RF) {
+      with_flags([&](auto ENV, auto DUR) {
+        hipLaunchKernelGGL((k_range_mask<RF(), ENV(), DUR()>), dim3((unsigned)nblocks), dim3(FTPB), 0, s,
+                           (const uint16_t*)bin, (const uint64_t*)z, coff, start, nr, total, d_desc, nxy, ff, b.mask,
+                           b.counts);
+      }, env, dur);
+    });
     GM_CHECK_LAUNCH();
     rc = finish_scan(ctx, total, b, ids, ids_cap, &nm);
     if (rc) return rc;

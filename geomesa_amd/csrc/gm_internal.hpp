@@ -9,6 +9,7 @@
 
 #include "../../include/geomesa_hip.h"
 #include "gm_device.hpp"
+#include "gm_dispatch.hpp"
 
 struct gm_ctx {
   int device = 0;
@@ -157,11 +158,24 @@ int end_summary(gm_ctx* ctx, gm_batch_status* summary, const uint8_t* status);
 // callers are safe); `fallback_per_cu` when the occupancy query fails.
 int resident_blocks(const void* kernel, int device, int block, int fallback_per_cu);
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+template <unsigned N>
+inline bool aligned_to(const void* p) { return ((uintptr_t)p & (N - 1)) == 0; }   // a null pointer is aligned
+inline bool aligned16(const void* p) { return aligned_to<16>(p); }
 
 inline unsigned grid_for(int64_t n, int64_t per_block) {
   int64_t b = (n + per_block - 1) / per_block;
   return (unsigned)(b < 1 ? 1 : b);
+}
+
+// grid of a pair kernel (one lane per two rows); a single row still gets its block
+inline unsigned pair_grid(int64_t n, int64_t pairs_per_block) {
+  return grid_for((n >> 1) > 0 ? (n >> 1) : 1, pairs_per_block);
+}
+
+// the answer of an indexing entry point to n == 0
+inline int empty_batch(gm_batch_status* summary) {
+  if (summary) *summary = gm_batch_status{0, -1, 0, 0};
+  return GM_OK;
 }
 
 }  // namespace gm

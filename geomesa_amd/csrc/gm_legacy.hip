@@ -132,7 +132,7 @@ int gm_legacy_z3_index(gm_ctx* ctx, const double* x, const double* y, const int6
                        int period, int lenient, int64_t* z, uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || !valid_period(period) || (curve != GM_LEGACY_Z3 && curve != GM_LEGACY_YEAR_Z3))
     return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!x || !y || !t || !z) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
@@ -145,13 +145,11 @@ int gm_legacy_z3_index(gm_ctx* ctx, const double* x, const double* y, const int6
   } else {
     // LegacyYearZ3Dimensions (LegacyYearZ3SFC.scala:38-45): NormalizedTime(21, 52 weeks in minutes)
     const NDim lon = lon_dim(21), lat = lat_dim(21), tim = make_ndim(0.0, 7.0 * 24 * 60 * 52, 21);
-    const int64_t ymax = max_offset(YEAR);
-    if (lenient)
-      hipLaunchKernelGGL((k_legacy_year_z3_index<true>), dim3(legacy_grid(n)), dim3(LTPB), 0, ctx->stream, x, y, t,
-                         n, lon, lat, tim, ymax, z, status, ctx->d_err);
-    else
-      hipLaunchKernelGGL((k_legacy_year_z3_index<false>), dim3(legacy_grid(n)), dim3(LTPB), 0, ctx->stream, x, y,
-                         t, n, lon, lat, tim, ymax, z, status, ctx->d_err);
+    const int64_t ymax = max_offset(GM_YEAR);
+    with_flags([&](auto L) {
+      hipLaunchKernelGGL((k_legacy_year_z3_index<L()>), dim3(legacy_grid(n)), dim3(LTPB), 0, ctx->stream, x, y, t, n,
+                         lon, lat, tim, ymax, z, status, ctx->d_err);
+    }, lenient != 0);
   }
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
@@ -173,7 +171,7 @@ int gm_legacy_z3_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int curve, int
 int gm_legacy_z2_index(gm_ctx* ctx, const double* x, const double* y, int64_t n, int lenient, int64_t* z,
                        uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0) return GM_E_INVALID;
-  if (n == 0) { if (summary) *summary = gm_batch_status{0, -1, 0, 0}; return GM_OK; }
+  if (n == 0) return empty_batch(summary);
   if (!x || !y || !z) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;

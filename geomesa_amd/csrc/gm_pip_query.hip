@@ -175,25 +175,6 @@ __global__ __launch_bounds__(QueryShape<OP>::TPB) void k_query_mask(const double
   }
   block_count_waves<TPB>(cnt, block_counts);
 }
-template <bool VEC, bool DURING>
-void launch_query(hipStream_t s, unsigned grid, int op, const double* x, const double* y, const int64_t* t, int64_t n,
-                  int has_bbox, const double* bb, int64_t lo, int64_t hi, const PipDev& d, uint64_t* mask,
-                  int32_t* counts) {
-  switch (op) {
-    case SP_INTERSECTS:
-      hipLaunchKernelGGL((k_query_mask<VEC, DURING, SP_INTERSECTS>), dim3(grid), dim3(QueryShape<SP_INTERSECTS>::TPB), 0, s, x, y, t, n, has_bbox,
-                         bb[0], bb[1], bb[2], bb[3], lo, hi, d, mask, counts);
-      break;
-    case SP_CONTAINS:
-      hipLaunchKernelGGL((k_query_mask<VEC, DURING, SP_CONTAINS>), dim3(grid), dim3(QueryShape<SP_CONTAINS>::TPB), 0, s, x, y, t, n, has_bbox,
-                         bb[0], bb[1], bb[2], bb[3], lo, hi, d, mask, counts);
-      break;
-    default:
-      hipLaunchKernelGGL((k_query_mask<VEC, DURING, SP_NONE>), dim3(grid), dim3(QueryShape<SP_NONE>::TPB), 0, s, x, y, t, n, has_bbox,
-                         bb[0], bb[1], bb[2], bb[3], lo, hi, d, mask, counts);
-  }
-}
-
 }  // namespace gm
 
 using namespace gm;
@@ -221,19 +202,16 @@ int gm_query_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t* 
   }
   const unsigned grid = (unsigned)((n + FROWS - 1) / FROWS);
   const bool vec = aligned16(x) && aligned16(y) && (!has_during || aligned16(t_ms));
-  if (vec) {
-    if (has_during) launch_query<true, true>(ctx->stream, grid, spatial_op, x, y, t_ms, n, bbox != nullptr, bb, lo, hi, d, b.mask, b.counts);
-    else launch_query<true, false>(ctx->stream, grid, spatial_op, x, y, t_ms, n, bbox != nullptr, bb, lo, hi, d, b.mask, b.counts);
-  } else {
-    if (has_during) launch_query<false, true>(ctx->stream, grid, spatial_op, x, y, t_ms, n, bbox != nullptr, bb, lo, hi, d, b.mask, b.counts);
-    else launch_query<false, false>(ctx->stream, grid, spatial_op, x, y, t_ms, n, bbox != nullptr, bb, lo, hi, d, b.mask, b.counts);
-  }
+  with_flags([&](auto V, auto D) {
+    with_value<SP_INTERSECTS, SP_CONTAINS, SP_NONE>(spatial_op, [&](auto OP) {
+      hipLaunchKernelGGL((k_query_mask<V(), D(), OP()>), dim3(grid), dim3(QueryShape<OP()>::TPB), 0, ctx->stream, x, y,
+                         t_ms, n, bbox != nullptr, bb[0], bb[1], bb[2], bb[3], lo, hi, d, b.mask, b.counts);
+    });
+  }, vec, has_during != 0);
   GM_CHECK_LAUNCH();
-  rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
-  if (rc) return rc;
-  if (spatial_op != GM_SPATIAL_NONE && (rc = take_fault(ctx, "gm_query_scan"))) return rc;
-  if (n_match && ids && *n_match > ids_cap) return GM_E_CAPACITY;
-  return GM_OK;
+  // the reference fault is answered before the capacity
+  return end_scan(ctx, n, b, ids, ids_cap, n_match,
+                  [&] { return spatial_op != GM_SPATIAL_NONE ? take_fault(ctx, "gm_query_scan") : (int)GM_OK; });
 }
 
 }  // extern "C"

@@ -193,4 +193,17 @@ int alloc_scan(gm_ctx* ctx, int64_t n, uint64_t* user_mask, size_t desc_words, S
 // passes B and C: block-count scan, ids in ascending row order, match count readback
 int finish_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_cap, int64_t* n_match);
 
+// A scan's epilogue: finish_scan, then whatever the scan reads back or answers first (`before`), then
+// GM_E_CAPACITY when the caller asked for both the count and the ids and ids[] was too short.
+template <class Before>
+int end_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_cap, int64_t* n_match, Before before) {
+  int rc = finish_scan(ctx, n, b, ids, ids_cap, n_match);
+  if (!rc) rc = before();
+  if (rc) return rc;
+  return n_match && ids && *n_match > ids_cap ? GM_E_CAPACITY : GM_OK;
+}
+inline int end_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_cap, int64_t* n_match) {
+  return end_scan(ctx, n, b, ids, ids_cap, n_match, [] { return (int)GM_OK; });
+}
+
 }  // namespace gm

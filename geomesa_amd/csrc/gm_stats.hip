@@ -377,14 +377,11 @@ int launch_hist(gm_ctx* ctx, const double* x, const double* y, const int64_t* t,
         GM_CHECK_LAUNCH();
         return GM_OK;
       };
-      int rc;
-      const bool top = a.top_s > 0;
-      if (vec && top)
-        rc = narrow ? go(k_z3_hist_lds<PERIOD, UNOBS, true, true, true>) : go(k_z3_hist_lds<PERIOD, UNOBS, true, false, true>);
-      else if (vec)
-        rc = narrow ? go(k_z3_hist_lds<PERIOD, UNOBS, true, true, false>) : go(k_z3_hist_lds<PERIOD, UNOBS, true, false, false>);
-      else
-        rc = narrow ? go(k_z3_hist_lds<PERIOD, UNOBS, false, true, false>) : go(k_z3_hist_lds<PERIOD, UNOBS, false, false, false>);
+      // TOP exists for the vector kernel only: six instantiations per (PERIOD, UNOBS), not eight
+      const int rc = with_flags([&](auto V, auto T, auto N) {
+        if constexpr (V()) return go(k_z3_hist_lds<PERIOD, UNOBS, true, N(), T()>);
+        else return go(k_z3_hist_lds<PERIOD, UNOBS, false, N(), false>);
+      }, vec, a.top_s > 0, narrow);
       if (rc) return rc;
     }
   } else {
@@ -393,13 +390,6 @@ int launch_hist(gm_ctx* ctx, const double* x, const double* y, const int64_t* t,
     GM_CHECK_LAUNCH();
   }
   return GM_OK;
-}
-
-template <int PERIOD>
-int launch_hist_p(gm_ctx* ctx, const double* x, const double* y, const int64_t* t, const HistArgs& a, bool unobs,
-                  uint8_t* present, unsigned long long* counts, unsigned long long* tally) {
-  return unobs ? launch_hist<PERIOD, true>(ctx, x, y, t, a, present, counts, tally)
-               : launch_hist<PERIOD, false>(ctx, x, y, t, a, present, counts, tally);
 }
 
 }  // namespace gm
@@ -446,13 +436,10 @@ int gm_z3_histogram(gm_ctx* ctx, const double* x, const double* y, const int64_t
   }
   unsigned long long* c = (unsigned long long*)counts;
   unsigned long long* tl = (unsigned long long*)tally;
-  const bool u = unobserve != 0;
-  switch (period) {
-    case DAY: return launch_hist_p<DAY>(ctx, x, y, t_ms, a, u, present, c, tl);
-    case WEEK: return launch_hist_p<WEEK>(ctx, x, y, t_ms, a, u, present, c, tl);
-    case MONTH: return launch_hist_p<MONTH>(ctx, x, y, t_ms, a, u, present, c, tl);
-    default: return launch_hist_p<YEAR>(ctx, x, y, t_ms, a, u, present, c, tl);
-  }
+  return with_period(period, [&](auto P) {
+    return with_flags([&](auto U) { return launch_hist<P(), U()>(ctx, x, y, t_ms, a, present, c, tl); },
+                      unobserve != 0);
+  });
 }
 
 }  // extern "C"

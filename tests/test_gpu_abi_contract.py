@@ -47,7 +47,7 @@ others as in "all"):
   gm_strict_scan    x, y, t_ms (with a during) at 16 B
       all                 k_strict_mask_v<true>;     x+1, y+1, t_ms+1   k_strict_mask<true>;   mask+1, ids+1
   gm_query_scan     x, y, t_ms (with a during) at 16 B, with a geometry term
-      all                 launch_query<true, true>;  x+1, y+1, t_ms+1   launch_query<false, true>;  mask+1, ids+1
+      all                 k_query_mask<VEC = true, true, ..>;  x+1, y+1, t_ms+1   k_query_mask<false, true, ..>;  mask+1, ids+1
   gm_z3_histogram   x, y, t_ms at 16 B (LDS-counter path)
       all                 k_z3_hist_lds<.., VEC = true, ..>;   x+1, y+1, t_ms+1   k_z3_hist_lds<.., false, ..>
       present+1, counts+1, tally+1   the same kernel, outputs at odd element offsets
@@ -109,8 +109,9 @@ def interleave_yx(x, y):
 
 # ---------------------------------------------------------------- 1. element failures
 # An index case: cols(rng, n) -> clean input columns; spoil(cols, bad) makes rows bad[0..2] fail; call(lib, h,
-# ins, n, outs, status, summary) -> rc with pointer lists; outs: output dtypes; expect(O, cols) -> (outputs,
-# status) from the oracle, failed rows zero.
+# ins, n, outs, status, summary, period, lenient) -> rc with pointer lists; outs: output dtypes; expect(O, cols,
+# period, lenient) -> (outputs, status) from the oracle, failed rows zero.  period and lenient default to WEEK
+# and strict, which every test of this file uses; test_gpu_dispatch.py walks the others.
 
 def xyt_ms(rng, n):
     return [rng.uniform(-180, 180, n), rng.uniform(-90, 90, n), rng.integers(T2020, T2021, n)]
@@ -161,64 +162,64 @@ class IndexCase:
 
 
 def _c_z3_index():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_z3_index(h, i[0], i[1], i[2], n, WEEK, 21, 0, o[0], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_z3_index(h, i[0], i[1], i[2], n, period, 21, lenient, o[0], st, sm)
 
-    def expect(O, c):
+    def expect(O, c, period=WEEK, lenient=False):
         return loop_expect(len(c[0]), lambda i: (lambda s, z: (s, [z]))(
-            *O.z3_index(c[0][i], c[1][i], int(c[2][i]), False, WEEK, 21)))([I64])
+            *O.z3_index(c[0][i], c[1][i], int(c[2][i]), lenient, period, 21)))([I64])
     return IndexCase(256, xyt_off, spoil_xyt(-1), [I64], call, expect)
 
 
 def _c_z3_index_key():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_z3_index_key(h, i[0], i[1], i[2], n, WEEK, 0, o[0], o[1], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_z3_index_key(h, i[0], i[1], i[2], n, period, lenient, o[0], o[1], st, sm)
 
-    def expect(O, c):
-        b, z, st = O.z3_index_key_batch(c[0], c[1], c[2], False, WEEK)
+    def expect(O, c, period=WEEK, lenient=False):
+        b, z, st = O.z3_index_key_batch(c[0], c[1], c[2], lenient, period)
         return [b, z], st
     return IndexCase(2048, xyt_ms, spoil_xyt(-5), [I16, I64], call, expect)
 
 
 def _c_z2_index():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_z2_index(h, i[0], i[1], n, 31, 0, o[0], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_z2_index(h, i[0], i[1], n, 31, lenient, o[0], st, sm)
 
     def spoil(c, bad):
         c[0][bad[0]] = 200.0
         c[1][bad[1]] = 90.5
         c[1][bad[2]] = -91.0
 
-    def expect(O, c):
-        z, st = O.z2_index_batch(c[0], c[1], False)
+    def expect(O, c, period=WEEK, lenient=False):
+        z, st = O.z2_index_batch(c[0], c[1], lenient)
         return [z], st
     return IndexCase(512, lambda rng, n: xyt_ms(rng, n)[:2], spoil, [I64], call, expect)
 
 
 def _c_binned_time():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_binned_time(h, i[0], n, WEEK, o[0], o[1], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_binned_time(h, i[0], n, period, o[0], o[1], st, sm)
 
     def spoil(c, bad):
         c[0][bad[0]] = -1
         c[0][bad[1]] = 32768 * 604800000     # past the last week a short holds
         c[0][bad[2]] = -2**62
 
-    def expect(O, c):
+    def expect(O, c, period=WEEK, lenient=False):
         n = len(c[0])
         b, o, st = np.zeros(n, I16), np.zeros(n, I64), np.zeros(n, U8)
         for i in range(n):     # as test_binned_time_parity: the oracle's values, failed rows included
-            st[i], b[i], o[i] = O.binned_time(WEEK, int(c[0][i]))
+            st[i], b[i], o[i] = O.binned_time(period, int(c[0][i]))
         return [b, o], st
     return IndexCase(256, lambda rng, n: [rng.integers(T2020, T2021, n)], spoil, [I16, I64], call, expect)
 
 
 def _c_xz2_index():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_xz2_index(h, i[0], i[1], i[2], i[3], n, 12, 0, o[0], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_xz2_index(h, i[0], i[1], i[2], i[3], n, 12, lenient, o[0], st, sm)
 
-    def expect(O, c):
-        out, st = O.xz2_index_batch(np.stack(c, 1), False, 12)
+    def expect(O, c, period=WEEK, lenient=False):
+        out, st = O.xz2_index_batch(np.stack(c, 1), lenient, 12)
         return [np.where(st != 0, 0, out)], st
     return IndexCase(512, envelopes, spoil_env, [I64], call, expect)
 
@@ -230,39 +231,40 @@ def _xz3_cols(rng, n):
 
 
 def _c_xz3_index():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_xz3_index(h, i[0], i[1], i[2], i[3], i[4], i[5], n, 12, WEEK, 0, o[0], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_xz3_index(h, i[0], i[1], i[2], i[3], i[4], i[5], n, 12, period, lenient, o[0], st, sm)
 
     def spoil(c, bad):
         c[3][bad[0]] = 181.0
         c[2][bad[1]] = c[5][bad[1]] + 1.0     # zmin > zmax: unordered
         c[5][bad[2]] = WEEK_MAX + 1.0
 
-    def expect(O, c):
-        out, st = O.xz3_index_batch(np.stack(c, 1), False, 12, WEEK)
+    def expect(O, c, period=WEEK, lenient=False):
+        out, st = O.xz3_index_batch(np.stack(c, 1), lenient, 12, period)
         return [np.where(st != 0, 0, out)], st
     return IndexCase(512, _xz3_cols, spoil, [I64], call, expect)
 
 
-def _xz3_key_row(O, x0, y0, x1, y1, t):
-    s, b, off = O.binned_time(WEEK, int(t))
+def _xz3_key_row(O, x0, y0, x1, y1, t, period=WEEK, lenient=False):
+    s, b, off = O.binned_time(period, int(t))
     if s:
         return s, [0, 0]
-    s, xz = O.xz3_index(x0, y0, float(off), x1, y1, float(off), lenient=False, g=12, period=WEEK)
+    s, xz = O.xz3_index(x0, y0, float(off), x1, y1, float(off), lenient=lenient, g=12, period=period)
     return s, [b, xz]
 
 
 def _c_xz3_index_key():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_xz3_index_key(h, i[0], i[1], i[2], i[3], i[4], n, 12, WEEK, 0, o[0], o[1], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_xz3_index_key(h, i[0], i[1], i[2], i[3], i[4], n, 12, period, lenient, o[0], o[1], st, sm)
 
     def spoil(c, bad):
         c[2][bad[0]] = 181.0
         c[4][bad[1]] = -5                     # bad time
         c[0][bad[2]] = c[2][bad[2]] + 1.0     # unordered
 
-    def expect(O, c):
-        return loop_expect(len(c[0]), lambda i: _xz3_key_row(O, c[0][i], c[1][i], c[2][i], c[3][i], c[4][i]))([I16, I64])
+    def expect(O, c, period=WEEK, lenient=False):
+        return loop_expect(len(c[0]), lambda i: _xz3_key_row(O, c[0][i], c[1][i], c[2][i], c[3][i], c[4][i], period,
+                                                                 lenient))([I16, I64])
     return IndexCase(256, lambda rng, n: envelopes(rng, n) + [rng.integers(T2020, T2021, n)], spoil, [I16, I64],
                      call, expect)
 
@@ -289,80 +291,82 @@ class _Ins:
 
 
 def _c_z3_key_arrow():
-    def call(lib, h, i, n, o, st, sm):
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
         a = _Ins(i)
-        return lib.gm_z3_index_key_arrow(h, ctypes.byref(a.g), ctypes.byref(a.t), n, WEEK, 0, o[0], o[1], st, sm)
+        return lib.gm_z3_index_key_arrow(h, ctypes.byref(a.g), ctypes.byref(a.t), n, period, lenient, o[0], o[1], st,
+                                             sm)
 
-    def expect(O, c):
-        b, z, st = O.z3_index_key_batch(c[0][1::2], c[0][0::2], c[1], False, WEEK)
+    def expect(O, c, period=WEEK, lenient=False):
+        b, z, st = O.z3_index_key_batch(c[0][1::2], c[0][0::2], c[1], lenient, period)
         return [b, z], st
     return IndexCase(2048, _arrow_cols, _spoil_arrow, [I16, I64], call, expect)
 
 
 def _c_z2_key_arrow():
-    def call(lib, h, i, n, o, st, sm):
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
         a = _Ins(i)
-        return lib.gm_z2_index_key_arrow(h, ctypes.byref(a.g), n, 0, o[0], st, sm)
+        return lib.gm_z2_index_key_arrow(h, ctypes.byref(a.g), n, lenient, o[0], st, sm)
 
     def spoil(c, bad):
         _spoil_arrow(c, bad)
         c[0][2 * bad[1]] = 90.5
 
-    def expect(O, c):
-        z, st = O.z2_index_batch(c[0][1::2], c[0][0::2], False)
+    def expect(O, c, period=WEEK, lenient=False):
+        z, st = O.z2_index_batch(c[0][1::2], c[0][0::2], lenient)
         return [z], st
     return IndexCase(512, _arrow_cols, spoil, [I64], call, expect)
 
 
 def _c_xz2_key_arrow():
-    def call(lib, h, i, n, o, st, sm):
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
         a = _Ins(i)
-        return lib.gm_xz2_index_key_arrow(h, ctypes.byref(a.g), n, 12, 0, o[0], st, sm)
+        return lib.gm_xz2_index_key_arrow(h, ctypes.byref(a.g), n, 12, lenient, o[0], st, sm)
 
     def spoil(c, bad):
         _spoil_arrow(c, bad)
         c[0][2 * bad[1]] = 90.5
 
-    def expect(O, c):
+    def expect(O, c, period=WEEK, lenient=False):
         x, y = c[0][1::2], c[0][0::2]
-        out, st = O.xz2_index_batch(np.stack([x, y, x, y], 1), False, 12)
+        out, st = O.xz2_index_batch(np.stack([x, y, x, y], 1), lenient, 12)
         return [np.where(st != 0, 0, out)], st
     return IndexCase(256, _arrow_cols, spoil, [I64], call, expect)
 
 
 def _c_xz3_key_arrow():
-    def call(lib, h, i, n, o, st, sm):
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
         a = _Ins(i)
-        return lib.gm_xz3_index_key_arrow(h, ctypes.byref(a.g), ctypes.byref(a.t), n, 12, WEEK, 0, o[0], o[1], st, sm)
+        return lib.gm_xz3_index_key_arrow(h, ctypes.byref(a.g), ctypes.byref(a.t), n, 12, period, lenient, o[0], o[1], st,
+                                              sm)
 
-    def expect(O, c):
+    def expect(O, c, period=WEEK, lenient=False):
         x, y = c[0][1::2], c[0][0::2]
-        return loop_expect(len(x), lambda i: _xz3_key_row(O, x[i], y[i], x[i], y[i], c[1][i]))([I16, I64])
+        return loop_expect(len(x), lambda i: _xz3_key_row(O, x[i], y[i], x[i], y[i], c[1][i], period, lenient))([I16, I64])
     return IndexCase(256, _arrow_cols, _spoil_arrow, [I16, I64], call, expect)
 
 
 def _c_legacy_z3_index():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_legacy_z3_index(h, i[0], i[1], i[2], n, 0, WEEK, 0, o[0], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_legacy_z3_index(h, i[0], i[1], i[2], n, 0, period, lenient, o[0], st, sm)
 
-    def expect(O, c):
+    def expect(O, c, period=WEEK, lenient=False):
         return loop_expect(len(c[0]), lambda i: (lambda s, z: (s, [z]))(
-            *O.legacy_z3_index(c[0][i], c[1][i], int(c[2][i]), False, WEEK)))([I64])
+            *O.legacy_z3_index(c[0][i], c[1][i], int(c[2][i]), lenient, period)))([I64])
     return IndexCase(256, xyt_off, spoil_xyt(-1), [I64], call, expect)
 
 
 def _c_legacy_z2_index():
-    def call(lib, h, i, n, o, st, sm):
-        return lib.gm_legacy_z2_index(h, i[0], i[1], n, 0, o[0], st, sm)
+    def call(lib, h, i, n, o, st, sm, period=WEEK, lenient=0):
+        return lib.gm_legacy_z2_index(h, i[0], i[1], n, lenient, o[0], st, sm)
 
     def spoil(c, bad):
         c[0][bad[0]] = 200.0
         c[1][bad[1]] = 90.5
         c[1][bad[2]] = -91.0
 
-    def expect(O, c):
+    def expect(O, c, period=WEEK, lenient=False):
         return loop_expect(len(c[0]), lambda i: (lambda s, z: (s, [z]))(
-            *O.legacy_z2_index(c[0][i], c[1][i], False)))([I64])
+            *O.legacy_z2_index(c[0][i], c[1][i], lenient)))([I64])
     return IndexCase(256, lambda rng, n: xyt_ms(rng, n)[:2], spoil, [I64], call, expect)
 
 
