@@ -1,7 +1,8 @@
 // gm_pip.hpp -- the point-in-polygon index shared by the join (gm_pip_join.hip), the row-wise
 // predicate (gm_pip_relate.hip), the fused query scan (gm_pip_query.hip) and the index build
-// (gm_pip_build.hip): its device view (PipDev), the cell-word encoding, and the exact locators a
-// kernel runs on a (cell, polygon) pair -- JTS 1.20 semantics throughout.
+// (gm_pip_build.hip and its units, gm_pip_build.hpp): its device view (PipDev) and the exact locators
+// a kernel runs on a (cell, polygon) pair -- JTS 1.20 semantics throughout.  The index's bytes (the
+// cell-word encoding, the blob records, the array order) are gm_pip_layout.hpp's.
 //
 // Reference path: ST_Contains = geom1.contains(geom2) (geomesa-spark-jts/.../udf/SpatialRelationFunctions.scala:29)
 // evaluated per candidate pair by GeoMesaJoinRelation.sweeplineJoin / OverlapAction
@@ -34,20 +35,9 @@
 #include <vector>
 
 #include "gm_internal.hpp"
+#include "gm_pip_layout.hpp"
 
 namespace gm {
-
-enum : int { LOC_EXTERIOR = 0, LOC_BOUNDARY = 1, LOC_INTERIOR = 2 };
-
-struct RingDev {
-  double minx, miny, maxx, maxy;  // ring envelope (empty ring: +inf/-inf)
-  double y0, inv_h;               // slab(y) = clamp(floor((y - y0) * inv_h), 0, ns - 1)
-  int32_t ns, slab_base;          // slab_off[slab_base .. slab_base + ns]
-};
-
-struct Edge {
-  double p1x, p1y, p2x, p2y;  // countSegment(p1 = ring[i], p2 = ring[i-1])
-};
 
 struct PipDev {
   const RingDev* rings;          // fallback slab walk
@@ -101,41 +91,11 @@ __device__ __forceinline__ void pip_fault(const PipDev& d, uint32_t code) {
 #endif
 
 
-#ifndef GM_CF_LOG
-#define GM_CF_LOG 3
-#endif
-#ifndef GM_MAX_CELLS_LOG
-#define GM_MAX_CELLS_LOG 26
-#endif
-constexpr int CF_LOG = GM_CF_LOG;   // coarse cell = 8 x 8 fine cells: the coarse table (<= 4 MB) stays L2-resident
-
-// cell word kinds (2 high bits; 30-bit payload)
-enum : uint32_t { CELL_INTERIOR = 0, CELL_BOUNDARY = 1, CELL_LIST = 2, CELL_EMPTY = 3 };
-// BOUNDARY payload: bit 29 set = compact blob index, else generic blob offset (16-B units)
-constexpr uint32_t BLOB_COMPACT = 1u << 29;
-// LIST payload: list_ent offset << 4 | count; count 15 = long list whose count is list_ent[offset]
-constexpr int LIST_LONG = 15;
-
 // is the blob reference of a BOUNDARY entry (payload `ref`, LINE words excluded) inside the index?
 __device__ __forceinline__ bool blob_ref_ok(const PipDev& d, uint32_t ref) {
   if (ref & BLOB_COMPACT) return (uint64_t)(ref & (BLOB_COMPACT - 1)) < (uint64_t)d.n_compact_lines;
   return (uint64_t)ref < (uint64_t)d.n_blob16;
 }
-
-// Compact blob (single-ring polygon, 4 * segments + breakpoints <= 30 in the cell): one or two
-// 128-B lines of 16 words in `compact`, addressed by line index.
-//   w0: int32 polygon | int32 meta (segments | lines << 8), w1: parity bits,
-//   segment j (p1x p1y p2x p2y) at words CSEG[j] = 2, 6, 10 (line 0), 16, 20, 24, 28 (line 1);
-//   every other word of the record is a breakpoint slot (+inf when unused).
-// The breakpoint count k = #(slots <= y) does not depend on slot order, so the record is evaluated
-// with static indexing, line by line: crossings = parity bit k + segment crossings, exactly the
-// RayCrossingCounter walk of a generic one-ring blob.
-constexpr int CSEG_MAX = 7;
-__host__ __device__ constexpr int cseg_word(int j) { return j < 3 ? 2 + 4 * j : 16 + 4 * (j - 3); }
-
-struct RingHdr {
-  int16_t n_edge, n_brk, flags, pad;
-};
 
 // the cell of v on a g-cell axis, clamped (NaN -> 0).  Branch-free: a clamp by maxNum / minNum (NaN -> 0)
 // instead of two early returns, which compiled to exec-mask branches in every stream step
@@ -515,11 +475,11 @@ struct gm_pip_index {
   gm::PipDev dev{};
   std::vector<void*> allocs;
   int32_t n_polys = 0;
-  int64_t n_entries = 0, n_boundary = 0, n_records = 0, n_slow = 0, n_cells = 0, blob_bytes = 0, n_compact = 0;
-  int64_t max_bnd_per_cell = 0;   // most BOUNDARY (cell, polygon) entries of any cell (exported layout statistic)
-  int64_t max_ent_per_cell = 0;   // most (cell, polygon) entries of any cell (exported layout statistic)
+  int64_t stat[gm::ST_COUNT] = {};   // the counters in exported order (ST_*)
   int64_t n_lines = 0;            // line shortcut entries (make_shortcut)
   const int32_t* list_poly = nullptr;   // polygon of each list_ent slot (the row-wise predicate's list search)
-  const void* arr[GM_PIP_INDEX_ARRAYS] = {};   // the device arrays in gm_pip_index_layout order
-  int64_t arr_bytes[GM_PIP_INDEX_ARRAYS] = {};
+  const void* arr[gm::ARR_COUNT] = {};   // the device arrays in gm_pip_index_layout order (ARR_*)
+  int64_t arr_bytes[gm::ARR_COUNT] = {};
 };
+static_assert(gm::ARR_COUNT == GM_PIP_INDEX_ARRAYS && gm::ST_COUNT == sizeof(gm_pip_index_layout::stats) / sizeof(int64_t),
+              "ARR_* and ST_* name the exported layout");

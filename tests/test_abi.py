@@ -71,7 +71,7 @@ def test_no_environment_selected_kernel_paths():
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".hpp")):
             names |= set(re.findall(r'getenv\(\s*"([A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
-            assert "getenv(v)" not in open(os.path.join(csrc, f)).read() or f == "gm_pip_build.hip", f
+            assert "getenv(v)" not in open(os.path.join(csrc, f)).read() or f == "gm_pip_build_host.hpp", f
     assert names <= {"GM_PIP_DEBUG"}, names
 
 
