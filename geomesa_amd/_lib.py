@@ -156,6 +156,8 @@ SIGNATURES = {
     "gm_sort_keys": (cint, [vp, vp, vp, vp, i64, vp, vp, vp, vp]),
     "gm_key_range_scan": (cint, [vp, vp, vp, vp, i64, vp, i64, vp, sz, vp, vp, i64, vp, vp]),
     "gm_table_scan": (cint, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp]),
+    "gm_table_scan_geom": (cint, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp]),
+    "gm_arrow_envelopes": (cint, [vp, vp, i64, vp, vp, vp, vp]),
     "gm_z2_key_bytes": (cint, [vp, vp, vp, i64, vp]),
     "gm_key_sample": (cint, [vp, vp, vp, vp, i64, i32, vp, vp]),
     "gm_key_partition": (cint, [vp, vp, vp, vp, i64, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]),

@@ -272,6 +272,20 @@ def points_to_columns(points, flip_axis=False):
     return x, y
 
 
+def envelopes(geoms, kind, flip_axis=False):
+    """(xmin, ymin, xmax, ymax) float64 device columns: Geometry.getEnvelopeInternal of every slot of an
+    Arrow geometry column (gm_arrow_envelopes); a null slot and an empty geometry get the JTS null
+    envelope (0, 0, -1, -1)."""
+    import torch
+    col = _as_geom(geoms, kind, flip_axis)
+    n = col.n
+    ctx = _lib.context()
+    env = torch.empty((4, max(n, 1)), dtype=torch.float64, device=col._coords.device)
+    check(ctx.lib.gm_arrow_envelopes(ctx.handle, ctypes.byref(col.c_struct()), n, *[ptr(env[k]) for k in range(4)]),
+          "gm_arrow_envelopes")
+    return tuple(env[k, :n] for k in range(4))
+
+
 class ArrowPolygonIndex:
     """The join index built from an Arrow Polygon / MultiPolygon column (null slots never match)."""
 

@@ -209,91 +209,7 @@ __global__ __launch_bounds__(ATPB) void k_points_soa(ArrowPts g, int64_t n, doub
 }
 
 // ------------------------------------------------------------------ envelopes (XZ keys)
-// org.locationtech.jts.geom.Envelope: expandToInclude(x, y) initialises a null envelope and
-// otherwise widens with strict compares (a NaN ordinate never widens); expandToInclude(Envelope)
-// skips a null envelope.  The null envelope reads back as (minx 0, maxx -1, miny 0, maxy -1).
-struct Env {
-  double minx, maxx, miny, maxy;
-  bool null_;
-};
-
-__device__ __forceinline__ Env env_null() { return Env{0.0, -1.0, 0.0, -1.0, true}; }
-
-__device__ __forceinline__ void env_expand(Env& e, double x, double y) {
-  if (e.null_) { e = Env{x, x, y, y, false}; return; }
-  if (x < e.minx) e.minx = x;
-  if (x > e.maxx) e.maxx = x;
-  if (y < e.miny) e.miny = y;
-  if (y > e.maxy) e.maxy = y;
-}
-
-__device__ __forceinline__ void env_merge(Env& e, const Env& o) {
-  if (o.null_) return;
-  if (e.null_) { e = o; return; }
-  if (o.minx < e.minx) e.minx = o.minx;
-  if (o.maxx > e.maxx) e.maxx = o.maxx;
-  if (o.miny < e.miny) e.miny = o.miny;
-  if (o.maxy > e.maxy) e.maxy = o.maxy;
-}
-
-struct ArrowGeom {
-  const void* c;
-  const uint8_t* valid;
-  int64_t voff;
-  const int32_t* o0;
-  const int32_t* o1;
-  const int32_t* o2;
-  int32_t type;
-  int32_t flip;
-};
-
-// CoordinateSequence.expandEnvelope over tuples [a, b)
-template <bool F32>
-__device__ __forceinline__ Env env_tuples(const ArrowGeom& g, int64_t a, int64_t b) {
-  Env e = env_null();
-  for (int64_t j = a; j < b; ++j) {
-    double x, y;
-    arrow_tuple<F32>(g.c, j, g.flip, x, y);
-    env_expand(e, x, y);
-  }
-  return e;
-}
-
-// Geometry.getEnvelopeInternal of slot i: a polygon's is its shell's (Polygon.computeEnvelopeInternal),
-// a multi geometry's the merge of its parts' (GeometryCollection.computeEnvelopeInternal)
-template <bool F32>
-__device__ Env geom_envelope(const ArrowGeom& g, int64_t i) {
-  switch (g.type) {
-    case GM_GEOM_POINT: {
-      Env e = env_null();
-      double x, y;
-      arrow_tuple<F32>(g.c, i, g.flip, x, y);
-      env_expand(e, x, y);
-      return e;
-    }
-    case GM_GEOM_LINESTRING:
-    case GM_GEOM_MULTIPOINT:
-      return env_tuples<F32>(g, g.o0[i], g.o0[i + 1]);
-    case GM_GEOM_POLYGON: {
-      const int32_t r0 = g.o0[i], r1 = g.o0[i + 1];
-      if (r1 <= r0) return env_null();
-      return env_tuples<F32>(g, g.o1[r0], g.o1[r0 + 1]);
-    }
-    case GM_GEOM_MULTILINESTRING: {
-      Env e = env_null();
-      for (int32_t l = g.o0[i]; l < g.o0[i + 1]; ++l) env_merge(e, env_tuples<F32>(g, g.o1[l], g.o1[l + 1]));
-      return e;
-    }
-    default: {   // GM_GEOM_MULTIPOLYGON
-      Env e = env_null();
-      for (int32_t p = g.o0[i]; p < g.o0[i + 1]; ++p) {
-        const int32_t r0 = g.o1[p], r1 = g.o1[p + 1];
-        if (r1 > r0) env_merge(e, env_tuples<F32>(g, g.o2[r0], g.o2[r0 + 1]));
-      }
-      return e;
-    }
-  }
-}
+// (Env, ArrowGeom and geom_envelope: gm_arrow.hpp)
 
 // XZ2IndexKeySpace / XZ3IndexKeySpace.toIndexKey over an Arrow geometry column; DIM 3 also bins the date
 template <int DIM, int PERIOD, bool LENIENT, bool F32>
@@ -375,26 +291,6 @@ void launch_xz_arrow(hipStream_t s, bool lenient, bool f32, ArrowGeom g, ArrowTi
     hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, L(), F()>), dim3(agrid(n)), dim3(ATPB), 0, s, g, tc, n, gp, zhi,
                        bin, xz, status, err);
   }, lenient, f32);
-}
-
-// the List offsets a geometry type needs, outermost first
-inline int offset_levels(int type) {
-  switch (type) {
-    case GM_GEOM_POINT: return 0;
-    case GM_GEOM_LINESTRING: case GM_GEOM_MULTIPOINT: return 1;
-    case GM_GEOM_POLYGON: case GM_GEOM_MULTILINESTRING: return 2;
-    case GM_GEOM_MULTIPOLYGON: return 3;
-    default: return -1;
-  }
-}
-
-inline bool geom_col_ok(const gm_geom_column* g) {
-  if (!g || !g->coords || (g->ordinal_bits != 64 && g->ordinal_bits != 32)) return false;
-  const int lv = offset_levels(g->type);
-  if (lv < 0) return false;
-  for (int k = 0; k < lv; ++k)
-    if (!g->offsets[k]) return false;
-  return true;
 }
 
 }  // namespace gm

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "gm_arrow.hpp"
 #include "gm_scan.hpp"
 
 namespace gm {
@@ -458,19 +459,6 @@ __global__ __launch_bounds__(1024) void k_scan_i64(int64_t* __restrict__ a, int6
   if (t == 1023) a[len] = part[1023];
 }
 
-// candidate c -> its range (upper_bound over the scanned offsets, minus one) -> table row
-__device__ __forceinline__ int64_t cand_row(const int64_t* __restrict__ coff, const int64_t* __restrict__ start,
-                                            int64_t nr, int64_t c) {
-  int64_t lo = 0, hi = nr;
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (coff[m] <= c) lo = m + 1; else hi = m;
-  }
-  const int64_t r = lo - 1;
-  return start[r] + (c - coff[r]);
-}
-
-
 // candidate-space mask: candidate c = the c-th row inside the (disjoint, sorted) intervals.  RF: the row
 // filter the tablet server runs on the key (RowFilterIterator.scala:52-66): none, Z3Filter.inBounds on
 // (bin, z) (Z3Filter.scala:26-62) or Z2Filter.inBounds on z (Z2Filter.scala:20-35).  ENV / DUR: the full
@@ -487,11 +475,6 @@ struct FullFilter {
   int64_t t_lo, t_hi;
   const int64_t* rows;                        // table row -> column row (null: the identity)
 };
-// JTS Envelope.intersects(Envelope): false for a null envelope (maxx < minx) on either side
-__device__ __forceinline__ bool env_intersects(double ax0, double ay0, double ax1, double ay1, const double* q) {
-  if (ax1 < ax0 || q[2] < q[0]) return false;
-  return !(q[0] > ax1 || q[2] < ax0 || q[1] > ay1 || q[3] < ay0);
-}
 template <int RF, bool ENV, bool DUR>
 __global__ __launch_bounds__(FTPB) void k_range_mask(const uint16_t* __restrict__ bin, const uint64_t* __restrict__ z,
                                                      const int64_t* __restrict__ coff, const int64_t* __restrict__ start,
@@ -867,15 +850,22 @@ int gm_strict_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t*
   return end_scan(ctx, n, b, ids, ids_cap, n_match);
 }
 
-int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
-                  const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f, const int64_t* perm,
-                  int64_t* ids, int64_t ids_cap, int64_t* n_match, int64_t* n_scanned) {
+}  // extern "C"
+
+// gm_table_scan and gm_table_scan_geom: the seek, the mask pass and the compaction.  geom = NULL is
+// gm_table_scan, launch for launch; with geom the survivors of the envelope pass are compacted as
+// candidate indices, refined against their geometries (geom_refine) and the mask is compacted again.
+static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
+                      const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
+                      const gm_geom_column* geom, const int64_t* perm, int64_t* ids, int64_t ids_cap,
+                      int64_t* n_match, int64_t* n_scanned, int64_t* n_envelope) {
+  const std::string who = geom ? "gm_table_scan_geom" : "gm_table_scan";   // the entry the error texts name
   if (!ctx || n < 0 || n_ranges < 0 || (n_ranges > 0 && !ranges) || ids_cap < 0) return GM_E_INVALID;
   if (n > 0 && !z) return GM_E_INVALID;
   gm_scan_filter none{};
   if (!f) f = &none;
-  if (f->z3filter && f->z2filter) return set_error("gm_table_scan: a Z3Filter and a Z2Filter together"), GM_E_INVALID;
-  if (f->z3filter && !bin) return set_error("gm_table_scan: a Z3Filter needs the bin column"), GM_E_INVALID;
+  if (f->z3filter && f->z2filter) return set_error(who + ": a Z3Filter and a Z2Filter together"), GM_E_INVALID;
+  if (f->z3filter && !bin) return set_error(who + ": a Z3Filter needs the bin column"), GM_E_INVALID;
   const bool env = f->n_boxes > 0, dur = f->during != 0;
   if (f->n_boxes < 0 || (env && (!f->boxes || !f->xmin || !f->ymin || !f->xmax || !f->ymax)) || (dur && !f->t_ms))
     return GM_E_INVALID;
@@ -884,14 +874,14 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
   int rf = RF_NONE, nxy = 0;
   if (f->z3filter) {
     if (!build_z3_desc(f->z3filter, f->z3filter_len, desc)) {
-      set_error("gm_table_scan: malformed Z3Filter bytes");
+      set_error(who + ": malformed Z3Filter bytes");
       return GM_E_INVALID;
     }
     rf = RF_Z3;
   } else if (f->z2filter) {
     if (f->z2filter_len < 4) return GM_E_INVALID;
     if (!build_z2_desc(f->z2filter, f->z2filter_len, desc)) {
-      set_error("gm_table_scan: malformed Z2Filter bytes");
+      set_error(who + ": malformed Z2Filter bytes");
       return GM_E_INVALID;
     }
     nxy = (int)(desc.size() / 4);
@@ -927,6 +917,7 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
   if (n == 0 || nr == 0) {
     if (n_match) *n_match = 0;
     if (n_scanned) *n_scanned = 0;
+    if (n_envelope) *n_envelope = 0;
     return GM_OK;
   }
   hipStream_t s = ctx->stream;
@@ -946,7 +937,7 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
   GM_HIP(hipStreamSynchronize(s));  // dr is pageable; the candidate count sizes the pass below
   const int64_t total = ctx->h_pinned[0];
   if (n_scanned) *n_scanned = total;
-  int64_t nm = 0;
+  int64_t nm = 0, ne = 0;
   if (total > 0) {
     // device descriptor: [query boxes f64 x 4 nbox][row-filter words]
     const size_t box_words = env ? (size_t)f->n_boxes * 8 : 0;
@@ -969,7 +960,20 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
       }, env, dur);
     });
     GM_CHECK_LAUNCH();
-    rc = finish_scan(ctx, total, b, ids, ids_cap, &nm);
+    if (geom) {
+      // the envelope pass's survivors as candidate indices, then the exact test clears the failing bits
+      if ((rc = finish_scan(ctx, total, b, nullptr, 0, &ne))) return rc;
+      int64_t* surv = nullptr;
+      if (ne > 0) {
+        if ((rc = tmp.alloc_async((size_t)ne * 8, &surv))) return rc;
+        hipLaunchKernelGGL(k_mask_to_ids, dim3((unsigned)nblocks), dim3(FTPB), 0, s, b.mask, total, b.offsets, surv, ne);
+        GM_CHECK_LAUNCH();
+        const GeomRefine gr{surv, ne, coff, start, nr, total, ff.rows, f->xmin, f->ymin, f->xmax, f->ymax, ff.boxes,
+                            f->n_boxes, b.mask, b.counts};
+        if ((rc = geom_refine(ctx, geom, gr))) return rc;
+      }
+    }
+    rc = (geom && ne == 0) ? GM_OK : finish_scan(ctx, total, b, ids, ids_cap, &nm);
     if (rc) return rc;
     const int64_t m = std::min(nm, ids_cap);
     if (ids && m > 0) {
@@ -979,8 +983,38 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
     }
   }
   if (n_match) *n_match = nm;
+  if (n_envelope) *n_envelope = ne;
   if (ids && nm > ids_cap) return GM_E_CAPACITY;
   return GM_OK;
+}
+
+extern "C" {
+
+int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
+                  const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f, const int64_t* perm,
+                  int64_t* ids, int64_t ids_cap, int64_t* n_match, int64_t* n_scanned) {
+  return table_scan(ctx, shard, bin, z, n, ranges, n_ranges, f, nullptr, perm, ids, ids_cap, n_match, n_scanned,
+                    nullptr);
+}
+
+int gm_table_scan_geom(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
+                       const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
+                       const gm_geom_column* geom, const int64_t* perm, int64_t* ids, int64_t ids_cap,
+                       int64_t* n_match, int64_t* n_scanned, int64_t* n_envelope) {
+  if (!ctx) return GM_E_INVALID;
+  if (!f) return set_error("gm_table_scan_geom: the filter (query boxes, envelope columns) is required"), GM_E_INVALID;
+  if (f->n_boxes <= 0) return set_error("gm_table_scan_geom: at least one query box is required"), GM_E_INVALID;
+  if (!f->boxes || !f->xmin || !f->ymin || !f->xmax || !f->ymax)
+    return set_error("gm_table_scan_geom: the boxes and the four envelope columns are required"), GM_E_INVALID;
+  if (!geom) return set_error("gm_table_scan_geom: the geometry column is required"), GM_E_INVALID;
+  if (geom->ordinal_bits != 64 && geom->ordinal_bits != 32)
+    return set_error("gm_table_scan_geom: ordinal_bits must be 64 or 32"), GM_E_INVALID;
+  if (geom->type < GM_GEOM_POINT || geom->type > GM_GEOM_MULTIPOLYGON)
+    return set_error("gm_table_scan_geom: unknown geometry type"), GM_E_INVALID;
+  if (!geom_col_ok(geom))
+    return set_error("gm_table_scan_geom: coords or a List offsets level of the geometry type is NULL"), GM_E_INVALID;
+  return table_scan(ctx, shard, bin, z, n, ranges, n_ranges, f, geom, perm, ids, ids_cap, n_match, n_scanned,
+                    n_envelope);
 }
 
 int gm_key_range_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,

@@ -1,0 +1,258 @@
+// gm_geom_filter.hip -- the XZ tables' full filter on the feature GEOMETRY: geometry meets query box.
+//
+// The XZ key spaces always apply the full filter (XZ2IndexKeySpace.scala:122-125,
+// XZ3IndexKeySpace.scala:247-250); for bbox(geom, ...) it is GeoTools BBOXImpl on the feature's geometry
+// (GeometryProcessing.scala:104-136), i.e. JTS Geometry.intersects against the query rectangle.  The
+// contract here is the closed-set one: slot G matches box B iff G and B share a point.  JTS 1.20
+// RectangleIntersects gets there by an envelope check, GeometryContainsPointVisitor over the
+// rectangle's corners and RectangleLineIntersector per segment; so does k_geom_refine:
+//   * the envelope test is the mask pass of the scan (k_range_mask, gm_filter.hip); its survivors come
+//     here as compacted candidate indices, one 64-lane wave per survivor;
+//   * lanes stride over the slot's segments (consecutive tuples: one contiguous run per wave step, each
+//     tuple loaded once, a segment's second end taken from the next lane).
+//     RectangleLineIntersector: segment envelope, an endpoint in the box, else the segment ordered by
+//     (x, y) against the diagonal of opposite slope, decided by four orientation signs
+//     (RobustLineIntersector; jts_orientation, gm_device.hpp) -- reached only when both endpoints are
+//     outside and the envelopes overlap;
+//   * a polygon also matches when the box lies inside it.  When no ring segment meets the box the box
+//     touches no ring, so its four corners have one location and the corner (xmin, ymin) stands for all
+//     of them: the same pass over a ring counts that corner's crossings (RayCrossingCounter.countSegment,
+//     gm_pip.hpp), a ballot gives the ring's parity, and SimplePointInAreaLocator's rule decides
+//     (inside the shell and inside no hole; not Mod-2 over the rings);
+//   * a survivor that meets no box clears its bit of the candidate mask; k_mask_recount then takes the
+//     per-block counts again and the scan's compaction runs as after pass A.
+// Two shortcuts follow from the definition and skip the walk: a slot envelope inside the box, and a
+// LineString / Polygon (one connected component reaching all four sides of its envelope) whose x- or
+// y-range lies within the box's.  Neither holds for the union envelope of a multi geometry.
+#include <algorithm>
+
+#include "gm_arrow.hpp"
+#include "gm_pip.hpp"
+#include "gm_scan.hpp"
+
+namespace gm {
+
+constexpr int GTPB = 256;   // 4 waves per block, one survivor per wave
+
+struct Box {
+  double x0, y0, x1, y1;
+};
+
+__device__ __forceinline__ bool pt_in_box(double x, double y, const Box& q) {
+  return x >= q.x0 && x <= q.x1 && y >= q.y0 && y <= q.y1;
+}
+
+// Envelope.intersects(p1, p2, q): q in the envelope of the segment p1-p2
+__device__ __forceinline__ bool pt_in_seg_env(double ax, double ay, double bx, double by, double qx, double qy) {
+  return qx >= (ax < bx ? ax : bx) && qx <= (ax > bx ? ax : bx) && qy >= (ay < by ? ay : by) &&
+         qy <= (ay > by ? ay : by);
+}
+
+// RectangleLineIntersector.intersects(p0, p1) for a non-null box
+__device__ __forceinline__ bool seg_meets_box(double ax, double ay, double bx, double by, const Box& q) {
+  const double sx0 = ax < bx ? ax : bx, sx1 = ax > bx ? ax : bx;
+  const double sy0 = ay < by ? ay : by, sy1 = ay > by ? ay : by;
+  if (q.x0 > sx1 || q.x1 < sx0 || q.y0 > sy1 || q.y1 < sy0) return false;
+  if (pt_in_box(ax, ay, q) || pt_in_box(bx, by, q)) return true;
+  // Coordinate.compareTo order, then the diagonal of opposite slope
+  if (ax > bx || (ax == bx && ay > by)) {
+    double t = ax; ax = bx; bx = t;
+    t = ay; ay = by; by = t;
+  }
+  const bool up = by > ay;
+  const double d0x = q.x0, d0y = up ? q.y1 : q.y0, d1x = q.x1, d1y = up ? q.y0 : q.y1;
+  // RobustLineIntersector.computeIntersect (the envelopes overlap: the diagonal's is the box)
+  const int pq1 = jts_orientation(ax, ay, bx, by, d0x, d0y);
+  const int pq2 = jts_orientation(ax, ay, bx, by, d1x, d1y);
+  if ((pq1 > 0 && pq2 > 0) || (pq1 < 0 && pq2 < 0)) return false;
+  const int qp1 = jts_orientation(d0x, d0y, d1x, d1y, ax, ay);
+  const int qp2 = jts_orientation(d0x, d0y, d1x, d1y, bx, by);
+  if ((qp1 > 0 && qp2 > 0) || (qp1 < 0 && qp2 < 0)) return false;
+  if ((pq1 | pq2 | qp1 | qp2) == 0)   // computeCollinearIntersection
+    return pt_in_seg_env(ax, ay, bx, by, d0x, d0y) || pt_in_seg_env(ax, ay, bx, by, d1x, d1y) ||
+           pt_in_seg_env(d0x, d0y, d1x, d1y, ax, ay) || pt_in_seg_env(d0x, d0y, d1x, d1y, bx, by);
+  return true;
+}
+
+// a List offset every lane of the wave reads alike, as a scalar
+__device__ __forceinline__ int32_t uoff(const int32_t* __restrict__ o, int64_t i) {
+  return __builtin_amdgcn_readfirstlane(o[i]);
+}
+
+// the tuples [a, b) as points: some point in the box
+template <bool F32>
+__device__ bool points_meet(const ArrowGeom& g, int32_t a, int32_t b, int lane, const Box& q) {
+  for (int32_t j0 = a; j0 < b; j0 += 64) {
+    const int32_t j = j0 + lane;
+    bool h = false;
+    if (j < b) {
+      double x, y;
+      arrow_tuple<F32>(g.c, j, g.flip, x, y);
+      h = pt_in_box(x, y, q);
+    }
+    if (__any(h)) return true;
+  }
+  return false;
+}
+
+// the tuples [a, b) as a line or a ring: some segment (j, j + 1), a <= j < b - 1, meets the box.  A wave
+// step reads one contiguous run of 64 tuples, one per lane, and takes each segment's second end from the
+// next lane, so a step covers 63 segments and no tuple is loaded twice within it.  RING also counts the
+// crossings of the corner (q.x0, q.y0) (on a segment: a hit) and gives the ring's parity
+template <bool F32, bool RING>
+__device__ bool line_meets(const ArrowGeom& g, int32_t a, int32_t b, int lane, const Box& q, bool& inside) {
+  int cross = 0;
+  for (int32_t j0 = a; j0 < b - 1; j0 += 63) {
+    const int32_t j = j0 + lane;
+    double ax = 0.0, ay = 0.0;
+    if (j < b) arrow_tuple<F32>(g.c, j, g.flip, ax, ay);
+    const double bx = __shfl_down(ax, 1, 64), by = __shfl_down(ay, 1, 64);
+    bool h = false;
+    if (lane < 63 && j < b - 1) {
+      h = seg_meets_box(ax, ay, bx, by, q);
+      if (RING && !h) h = count_segment(ax, ay, bx, by, q.x0, q.y0, cross);
+    }
+    if (__any(h)) return true;
+  }
+  if (RING) inside = __popcll(__ballot(cross & 1)) & 1;
+  return false;
+}
+
+// the rings [r0, r1) of `ro` as one polygon, shell first: a ring segment meets the box, or the box's
+// corner is inside the shell and inside no hole (SimplePointInAreaLocator.locatePointInPolygon)
+template <bool F32>
+__device__ bool polygon_meets(const ArrowGeom& g, const int32_t* __restrict__ ro, int32_t r0, int32_t r1, int lane,
+                              const Box& q) {
+  bool in_shell = false, in_hole = false;
+  for (int32_t r = r0; r < r1; ++r) {
+    bool in = false;
+    if (line_meets<F32, true>(g, uoff(ro, r), uoff(ro, r + 1), lane, q, in)) return true;
+    if (r == r0) in_shell = in; else in_hole |= in;
+  }
+  return in_shell && !in_hole;
+}
+
+// slot i meets the box (wave-uniform; every lane of the wave calls it with the same i and q)
+template <bool F32>
+__device__ bool geom_meets_box(const ArrowGeom& g, int64_t i, int lane, const Box& q) {
+  bool unused;
+  switch (g.type) {
+    case GM_GEOM_POINT: {
+      double x, y;
+      arrow_tuple<F32>(g.c, i, g.flip, x, y);
+      return pt_in_box(x, y, q);
+    }
+    case GM_GEOM_MULTIPOINT:
+      return points_meet<F32>(g, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
+    case GM_GEOM_LINESTRING:
+      return line_meets<F32, false>(g, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q, unused);
+    case GM_GEOM_POLYGON:
+      return polygon_meets<F32>(g, g.o1, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
+    case GM_GEOM_MULTILINESTRING: {
+      const int32_t l1 = uoff(g.o0, i + 1);
+      for (int32_t l = uoff(g.o0, i); l < l1; ++l)
+        if (line_meets<F32, false>(g, uoff(g.o1, l), uoff(g.o1, l + 1), lane, q, unused)) return true;
+      return false;
+    }
+    default: {   // GM_GEOM_MULTIPOLYGON
+      const int32_t p1 = uoff(g.o0, i + 1);
+      for (int32_t p = uoff(g.o0, i); p < p1; ++p)
+        if (polygon_meets<F32>(g, g.o2, uoff(g.o1, p), uoff(g.o1, p + 1), lane, q)) return true;
+      return false;
+    }
+  }
+}
+
+template <bool F32>
+__global__ __launch_bounds__(GTPB) void k_geom_refine(ArrowGeom g, GeomRefine a) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t nwaves = (int64_t)gridDim.x * (GTPB / 64);
+  const bool connected = g.type == GM_GEOM_LINESTRING || g.type == GM_GEOM_POLYGON;
+  for (int64_t s = (int64_t)blockIdx.x * (GTPB / 64) + wave; s < a.n_surv; s += nwaves) {
+    const int64_t c = a.surv[s];
+    const int64_t row = cand_row(a.coff, a.start, a.nr, c);
+    const int64_t r = a.rows ? a.rows[row] : row;
+    bool hit = false;
+    if (arrow_valid(g.valid, g.voff, r)) {
+      const double ex0 = a.xmin[r], ey0 = a.ymin[r], ex1 = a.xmax[r], ey1 = a.ymax[r];
+      for (int k = 0; k < a.nbox && !hit; ++k) {
+        const double* b = a.boxes + 4 * k;
+        if (!env_intersects(ex0, ey0, ex1, ey1, b)) continue;
+        const Box q{b[0], b[1], b[2], b[3]};
+        const bool xin = ex0 >= q.x0 && ex1 <= q.x1, yin = ey0 >= q.y0 && ey1 <= q.y1;
+        hit = (xin && yin) || (connected && (xin || yin)) || geom_meets_box<F32>(g, r, lane, q);
+      }
+    }
+    if (!hit && lane == 0) atomicAnd((unsigned long long*)&a.mask[c >> 6], ~(1ull << (c & 63)));
+  }
+}
+
+// per-block match counts of a candidate mask (the block_counts of pass A), one wave per block
+__global__ __launch_bounds__(64) void k_mask_recount(const uint64_t* __restrict__ mask, int64_t total,
+                                                     int32_t* __restrict__ counts) {
+  int c = 0;
+  for (int w = threadIdx.x; w < FROWS / 64; w += 64) {
+    const int64_t word = (int64_t)blockIdx.x * (FROWS / 64) + w;
+    if ((word << 6) < total) c += __popcll(mask[word]);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+  if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// Geometry.getEnvelopeInternal of every slot; a null slot reads as the null envelope
+template <bool F32>
+__global__ __launch_bounds__(GTPB) void k_arrow_envelopes(ArrowGeom g, int64_t n, double* __restrict__ xmin,
+                                                          double* __restrict__ ymin, double* __restrict__ xmax,
+                                                          double* __restrict__ ymax) {
+  for (int64_t i = (int64_t)blockIdx.x * GTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GTPB) {
+    const Env e = arrow_valid(g.valid, g.voff, i) ? geom_envelope<F32>(g, i) : env_null();
+    xmin[i] = e.minx;
+    ymin[i] = e.miny;
+    xmax[i] = e.maxx;
+    ymax[i] = e.maxy;
+  }
+}
+
+static ArrowGeom to_geom(const gm_geom_column* c) {
+  return ArrowGeom{c->coords, c->validity, c->validity_offset, c->offsets[0], c->offsets[1], c->offsets[2], c->type,
+                   c->flip_axis};
+}
+
+int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a) {
+  const ArrowGeom g = to_geom(geom);
+  const int64_t blocks = std::min<int64_t>((a.n_surv + GTPB / 64 - 1) / (GTPB / 64), 1 << 20);
+  with_flags([&](auto F) {
+    hipLaunchKernelGGL((k_geom_refine<F()>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, a);
+  }, geom->ordinal_bits == 32);
+  GM_CHECK_LAUNCH();
+  const int64_t nblocks = (a.total + FROWS - 1) / FROWS;
+  hipLaunchKernelGGL(k_mask_recount, dim3((unsigned)nblocks), dim3(64), 0, ctx->stream, a.mask, a.total, a.counts);
+  GM_CHECK_LAUNCH();
+  return GM_OK;
+}
+
+}  // namespace gm
+
+using namespace gm;
+
+extern "C" {
+
+int gm_arrow_envelopes(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, double* xmin, double* ymin, double* xmax,
+                       double* ymax) {
+  if (!ctx || n < 0) return GM_E_INVALID;
+  if (n == 0) return GM_OK;
+  if (!geom_col_ok(geom) || !xmin || !ymin || !xmax || !ymax) return GM_E_INVALID;
+  GM_HIP(hipSetDevice(ctx->device));
+  const ArrowGeom g = to_geom(geom);
+  const int64_t blocks = std::min<int64_t>((n + GTPB - 1) / GTPB, 256 * 32);
+  with_flags([&](auto F) {
+    hipLaunchKernelGGL((k_arrow_envelopes<F()>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, n, xmin, ymin,
+                       xmax, ymax);
+  }, geom->ordinal_bits == 32);
+  GM_CHECK_LAUNCH();
+  return GM_OK;
+}
+
+}  // extern "C"

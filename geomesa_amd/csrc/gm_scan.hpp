@@ -206,4 +206,40 @@ inline int end_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t i
   return end_scan(ctx, n, b, ids, ids_cap, n_match, [] { return (int)GM_OK; });
 }
 
+// ------------------------------------------------------------------ candidate space of a table scan
+// candidate c -> its range (upper_bound over the scanned offsets, minus one) -> table row
+__device__ __forceinline__ int64_t cand_row(const int64_t* __restrict__ coff, const int64_t* __restrict__ start,
+                                            int64_t nr, int64_t c) {
+  int64_t lo = 0, hi = nr;
+  while (lo < hi) {
+    const int64_t m = (lo + hi) >> 1;
+    if (coff[m] <= c) lo = m + 1; else hi = m;
+  }
+  const int64_t r = lo - 1;
+  return start[r] + (c - coff[r]);
+}
+
+// JTS Envelope.intersects(Envelope): false for a null envelope (maxx < minx) on either side
+__device__ __forceinline__ bool env_intersects(double ax0, double ay0, double ax1, double ay1, const double* q) {
+  if (ax1 < ax0 || q[2] < q[0]) return false;
+  return !(q[0] > ax1 || q[2] < ax0 || q[1] > ay1 || q[3] < ay0);
+}
+
+// The exact full filter of gm_table_scan_geom (gm_geom_filter.hip) over the survivors of the envelope
+// pass: candidate surv[s] keeps its bit of `mask` iff its geometry slot meets one of the boxes; then
+// the per-block counts are taken again from the mask, so finish_scan runs on it as on pass A's output.
+struct GeomRefine {
+  const int64_t* surv;                          // surviving candidate indices, ascending
+  int64_t n_surv;
+  const int64_t *coff, *start;                  // candidate -> table row (cand_row)
+  int64_t nr, total;
+  const int64_t* rows;                          // table row -> column row (null: the identity)
+  const double *xmin, *ymin, *xmax, *ymax;      // the slots' JTS envelopes (column order)
+  const double* boxes;                          // nbox x (xmin, ymin, xmax, ymax), device
+  int nbox;
+  uint64_t* mask;
+  int32_t* counts;
+};
+int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a);
+
 }  // namespace gm

@@ -271,6 +271,8 @@ class _KeyTable:
         import torch
         from .curve import _dev_col
         self.ctx = _lib.context()
+        self.geom = None         # the features' GeometryColumn (from_geometries); None: an envelope-only table
+        self.n_envelope = None   # of the last exact scan: the candidates its envelope test let through
         z = _dev_col(z, torch.int64)
         self.n = z.numel()
         dev = z.device
@@ -300,22 +302,51 @@ class _KeyTable:
                   "gm_z2_key_bytes")
         return out
 
-    def table_scan(self, arr, flt=None, map_rows=True, ids_cap=None):
+    def table_scan(self, arr, flt=None, map_rows=True, ids_cap=None, geom=None):
         """gm_table_scan over gm_key_range rows `arr` with a ScanFilter (None = no filter): (ids, n_match,
-        n_scanned); ids are input rows (map_rows) or table rows."""
+        n_scanned); ids are input rows (map_rows) or table rows.  With geom (a GeometryColumn in the order
+        of flt's envelope columns) the full filter is exact, geometry against box (gm_table_scan_geom), and
+        self.n_envelope keeps the number of candidates the envelope test let through."""
         import torch
         arr = np.ascontiguousarray(arr, _lib.KEY_RANGE_DTYPE)
         cap = self.n if ids_cap is None else ids_cap
         ids = torch.empty(max(cap, 1), dtype=torch.int64, device=self.z.device)
-        nm, ns = ctypes.c_int64(), ctypes.c_int64()
-        rc = self.ctx.lib.gm_table_scan(self.ctx.handle, ptr(self.shard), ptr(self.bin), ptr(self.z), self.n,
-                                        arr.ctypes.data if len(arr) else None, len(arr),
-                                        ctypes.byref(flt) if flt is not None else None,
-                                        ptr(self.perm) if map_rows else None, ptr(ids), cap, ctypes.byref(nm),
-                                        ctypes.byref(ns))
+        nm, ns, ne = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        head = (self.ctx.handle, ptr(self.shard), ptr(self.bin), ptr(self.z), self.n,
+                arr.ctypes.data if len(arr) else None, len(arr), ctypes.byref(flt) if flt is not None else None)
+        tail = (ptr(self.perm) if map_rows else None, ptr(ids), cap, ctypes.byref(nm), ctypes.byref(ns))
+        if geom is None:
+            what, rc = "gm_table_scan", self.ctx.lib.gm_table_scan(*head, *tail)
+        else:
+            what, rc = "gm_table_scan_geom", self.ctx.lib.gm_table_scan_geom(
+                *head, ctypes.byref(geom.c_struct()), *tail, ctypes.byref(ne))
+            self.n_envelope = ne.value
         if rc != _lib.GM_E_CAPACITY:
-            check(rc, "gm_table_scan")
+            check(rc, what)
         return ids[:min(nm.value, cap)], nm.value, ns.value
+
+    def _exact_geom(self, exact):
+        """query()'s exact argument -> the geometry column to filter on, or None for the envelope filter."""
+        if exact is None:
+            return self.geom
+        if exact and self.geom is None:
+            from .curve import IllegalArgumentException
+            raise IllegalArgumentException("exact=True needs a table that holds geometries (from_geometries)")
+        return self.geom if exact else None
+
+
+def _geometry_envelopes(geoms, kind, flip_axis):
+    """from_geometries' first steps: the GeometryColumn, its envelope columns, and the envelopes the keys
+    are taken from.  The reference has no key for a null or empty geometry (toIndexKey throws: "Null
+    geometry in feature", XZ2IndexKeySpace.scala:48-58); here such a slot keeps its table row, keyed as
+    the point (0, 0), and its null envelope keeps it out of every full-filter result."""
+    import torch
+    from . import arrow as A
+    col = A.GeometryColumn(geoms, kind, flip_axis) if not isinstance(geoms, A.GeometryColumn) else geoms
+    env = A.envelopes(col, kind)
+    null = env[2] < env[0]
+    zero = torch.zeros((), dtype=torch.float64, device=env[0].device)
+    return col, env, tuple(torch.where(null, zero, c) for c in env)
 
 
 def _full_filter(cols, boxes, interval=None, t=None, perm=None):
@@ -379,14 +410,26 @@ class XZ2Table(_KeyTable):
         self.env = tuple(_dev_col(c, torch.float64) for c in (xmin, ymin, xmax, ymax))
         super().__init__(None, self.ks.sfc.index(*self.env, lenient=lenient), shard, shards)
 
-    def query(self, bboxes=None, target=2000, full_filter=True):
+    @classmethod
+    def from_geometries(cls, geoms, kind, shard=None, shards=None, g=12, lenient=False, flip_axis=False):
+        """The table of an Arrow geometry column (a pyarrow Array or a GeometryColumn): keys from the
+        envelopes gm_arrow_envelopes gives, and the column kept for the exact full filter."""
+        col, env, key_env = _geometry_envelopes(geoms, kind, flip_axis)
+        tb = cls(*key_env, shard=shard, shards=shards, g=g, lenient=lenient)
+        tb.env, tb.geom = env, col
+        return tb
+
+    def query(self, bboxes=None, target=2000, full_filter=True, exact=None):
+        """exact: the full filter on the geometries (BBOX itself) rather than on their envelopes; None =
+        exact when the table holds geometries."""
+        geom = self._exact_geom(exact)
         v = self.ks.get_index_values(bboxes)
         if v.disjoint:
             import torch
             return torch.zeros(0, dtype=torch.int64, device=self.z.device), 0, 0
         arr, _ = key_ranges(self.ks.get_ranges(v, target=target), self.shards)
         f, keep = _full_filter(self.env, v.spatialBounds, perm=self.perm) if full_filter else (None, [])
-        return self.table_scan(arr, f)
+        return self.table_scan(arr, f, geom=geom if full_filter else None)
 
 
 class XZ3Table(_KeyTable):
@@ -412,13 +455,23 @@ class XZ3Table(_KeyTable):
         _raise_first(st, "XZ3IndexKeySpace.toIndexKey")
         super().__init__(b, xz, shard, shards)
 
-    def query(self, bboxes=None, interval=None, target=2000, full_filter=True):
-        """interval: (lo, hi) epoch millis of `dtg DURING lo/hi`, or None."""
+    @classmethod
+    def from_geometries(cls, geoms, dtg, kind, shard=None, shards=None, g=12, period="week", lenient=False,
+                        flip_axis=False):
+        """As XZ2Table.from_geometries, with the features' dtg column (epoch millis)."""
+        col, env, key_env = _geometry_envelopes(geoms, kind, flip_axis)
+        tb = cls(*key_env, dtg, shard=shard, shards=shards, g=g, period=period, lenient=lenient)
+        tb.env, tb.geom = env, col
+        return tb
+
+    def query(self, bboxes=None, interval=None, target=2000, full_filter=True, exact=None):
+        """interval: (lo, hi) epoch millis of `dtg DURING lo/hi`, or None.  exact: as XZ2Table.query."""
         from .keyspace import during
+        geom = self._exact_geom(exact)
         v = self.ks.get_index_values(bboxes, [during(*interval)] if interval is not None else None)
         if v.disjoint:
             import torch
             return torch.zeros(0, dtype=torch.int64, device=self.z.device), 0, 0
         arr, _ = key_ranges(self.ks.get_ranges(v, target=target), self.shards)
         f, keep = _full_filter(self.env, v.spatialBounds, interval, self.t, self.perm) if full_filter else (None, [])
-        return self.table_scan(arr, f)
+        return self.table_scan(arr, f, geom=geom if full_filter else None)

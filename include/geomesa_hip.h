@@ -452,6 +452,10 @@ int gm_xz2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, i
 int gm_xz3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* dtg, int64_t n, int g,
                            int period, int lenient, int16_t* bin, int64_t* xz, uint8_t* status,
                            gm_batch_status* summary);
+/* Geometry.getEnvelopeInternal of every slot as four device columns (a null slot and an empty geometry:
+   the JTS null envelope, 0, 0, -1, -1): the envelope columns of gm_scan_filter.  Asynchronous. */
+int gm_arrow_envelopes(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, double* xmin, double* ymin,
+                       double* xmax, double* ymax);
 /* A point column as x / y device columns (null slots -> NaN): the adapter for every other entry */
 int gm_arrow_points_to_columns(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, double* x, double* y);
 /* gm_pip_join_pred over an Arrow point column (null points never match): the direct pass reads the
@@ -547,8 +551,8 @@ int gm_key_range_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
      ends and NaN take no part in that rule), and with during != 0 the feature's dtg (t_ms: device, same
      order as the envelopes) lies in (t_lo, t_hi), exclusive (FastDuring,
      FastTemporalOperator.scala:116-129).  For a rectangular geometry the envelope test is GeoTools
-     BBOX exactly; for other geometries it is BBOX's envelope pre-check (geometry-geometry relations
-     are out of scope);
+     BBOX exactly; for other geometries it is BBOX's envelope pre-check, and gm_table_scan_geom applies
+     BBOX itself, on the feature geometry;
    - rows (device, optional): the column row of each table row, i.e. where table row r's envelope and
      dtg are found (xmin[rows[r]], ...).  NULL: gm_table_scan's perm argument maps them (columns in
      INPUT order); both NULL: the columns are in table order.  rows only reaches the full filter's
@@ -579,6 +583,26 @@ typedef struct {
 int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
                   const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f, const int64_t* perm,
                   int64_t* ids, int64_t ids_cap, int64_t* n_match, int64_t* n_scanned);
+
+/* gm_table_scan with the full filter on the feature GEOMETRY: a candidate must pass everything
+   gm_table_scan asks of it and its geometry (slot of geom, any GM_GEOM_* kind) must meet at least one of
+   f's boxes, each box [xmin, xmax] x [ymin, ymax] a closed set, a segment or a point included: GeoTools
+   BBOX on the geometry (geomesa-filter/.../GeometryProcessing.scala:104-136), i.e. JTS Geometry.intersects
+   with the rectangle (RectangleIntersects).  A point or multipoint has a point in the box; a line has a
+   segment meeting it; a polygon has a ring segment (shell or hole) meeting it or holds the box (inside the
+   shell and inside no hole, SimplePointInAreaLocator).  A null slot, an empty geometry and a null box
+   (xmax < xmin) never match.  Required, else GM_E_INVALID with a gm_last_error text: f, f->n_boxes > 0,
+   f->boxes, f's four envelope columns, geom with ordinal_bits 64 or 32, a GM_GEOM_* type and the coords and
+   List offsets of that type.  f's envelope columns must hold the slots' JTS envelopes (gm_arrow_envelopes
+   writes them): the envelope test stays the prefilter and decides the slots it can decide.  Table row r's
+   slot is found as its envelope is: f->rows, else perm, else the identity.  *n_envelope (host, optional)
+   receives the candidates that pass the row filter, during and the envelope test -- gm_table_scan's *n_match
+   for the same arguments.  ids, ids_cap, *n_match, *n_scanned, GM_E_CAPACITY and the synchronisation are
+   gm_table_scan's. */
+int gm_table_scan_geom(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
+                       const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
+                       const gm_geom_column* geom, const int64_t* perm, int64_t* ids, int64_t ids_cap,
+                       int64_t* n_match, int64_t* n_scanned, int64_t* n_envelope);
 
 /* ------------------------------------------------------------------ legacy curves (reading / deleting old data) */
 /* LegacyZ3SFC(period) (z3/curve/LegacyZ3SFC.scala:18-49): SemiNormalizedDimension lon/lat (2^21-1) and
