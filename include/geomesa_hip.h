@@ -67,6 +67,16 @@ extern "C" {
 #define GM_ST_UNORDERED 3     /* XZ require(xmin <= xmax ...) / ZRange require(min <= max) */
 #define GM_ST_NULL_GEOM 4     /* toIndexKey: "Null geometry in feature" (Z3IndexKeySpace.scala:66-68) */
 
+/* query_status values of the ranges entry points only (gm_z3_ranges, gm_z2_ranges, gm_zranges, gm_xz2_ranges,
+   gm_xz3_ranges), beside GM_ST_OUT_OF_BOUNDS and GM_ST_UNORDERED.  They are limits of this library, not
+   exceptions of the Scala code, and they are never written to a per-element status[].  The values are those of
+   GM_ST_NULL_GEOM and the next free one: in a query_status, 4 is GM_QS_CAPACITY and never means a null
+   geometry.  A query with either status delivers no ranges and does not count in *needed; the other queries
+   of the batch are not affected. */
+#define GM_QS_CAPACITY 4         /* range workspace capacity exceeded: an unbounded (max_ranges <= 0) query, or one
+                                    with a budget past the unbounded caps, whose walk outgrew its workspace */
+#define GM_QS_TOO_MANY_BOUNDS 5  /* more than 256 z-bounds (boxes x intervals) or windows in one query */
+
 /* TimePeriod (z3/curve/BinnedTime.scala:283-291) */
 #define GM_DAY 0
 #define GM_WEEK 1

@@ -199,17 +199,20 @@ def zranges(dims, bounds, precision=64, max_ranges=None, max_recurse=7):
     return _ranges_call(lib().gmo_zranges, dims, _p(b), len(b) // 2, precision, mr, rec)
 
 
-def z3_ranges(xy, t, precision=64, max_ranges=None, period=WEEK):
+def z3_ranges(xy, t, precision=64, max_ranges=None, period=WEEK, sfc_precision=21):
+    """Z3SFC(period, sfc_precision).ranges; `precision` is the range precision of ZN.zranges."""
     a = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1))
     tt = np.ascontiguousarray(np.asarray(t, dtype=np.int64).reshape(-1))
     mr = 2147483647 if max_ranges is None else max_ranges
-    return _ranges_call(lib().gmo_z3_ranges, period, 21, _p(a), len(a) // 4, _p(tt), len(tt) // 2, precision, mr)
+    return _ranges_call(lib().gmo_z3_ranges, period, sfc_precision, _p(a), len(a) // 4, _p(tt), len(tt) // 2,
+                        precision, mr)
 
 
-def z2_ranges(xy, precision=64, max_ranges=None):
+def z2_ranges(xy, precision=64, max_ranges=None, sfc_precision=31):
+    """Z2SFC(sfc_precision).ranges; `precision` is the range precision of ZN.zranges."""
     a = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1))
     mr = 2147483647 if max_ranges is None else max_ranges
-    return _ranges_call(lib().gmo_z2_ranges, 31, _p(a), len(a) // 4, precision, mr)
+    return _ranges_call(lib().gmo_z2_ranges, sfc_precision, _p(a), len(a) // 4, precision, mr)
 
 
 def nodes_checked():
