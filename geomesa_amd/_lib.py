@@ -86,6 +86,14 @@ class PolySetC(ctypes.Structure):
                 ("ring_vert_off", ctypes.c_void_p), ("vx", ctypes.c_void_p), ("vy", ctypes.c_void_p)]
 
 
+class DensityGrid(ctypes.Structure):
+    """gm_density_grid: the rendering envelope and pixel counts of a density scan, the launch's workgroup
+    count (0 = default) and the accumulation path (0 automatic, 1 LDS counters, 2 device atomics)."""
+    _fields_ = [("xmin", ctypes.c_double), ("ymin", ctypes.c_double), ("xmax", ctypes.c_double),
+                ("ymax", ctypes.c_double), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("workgroups", ctypes.c_int32), ("path", ctypes.c_int32)]
+
+
 GM_PIP_INDEX_ARRAYS = 8
 GM_PIP_LAYOUT_VERSION = 1
 
@@ -174,6 +182,9 @@ SIGNATURES = {
     "gm_legacy_z2_index": (cint, [vp, vp, vp, i64, cint, vp, vp, vp]),
     "gm_legacy_z2_invert": (cint, [vp, vp, i64, vp, vp]),
     "gm_z3_histogram": (cint, [vp, vp, vp, vp, i64, cint, cint, cint, cint, cint, vp, vp, vp]),
+    "gm_density_points": (cint, [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
+    "gm_density_arrow": (cint, [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
+    "gm_density_sparse": (cint, [vp, vp, i32, i32, i64, vp, vp, vp, vp]),
     "gm_gen_points": (cint, [vp, ctypes.c_uint64, i64, i64, d, d, d, d, i64, i64, vp, vp, vp]),
 }
 

@@ -647,6 +647,80 @@ int gm_z3_histogram(gm_ctx* ctx, const double* x, const double* y, const int64_t
                     int length, int unobserve, int bin_lo, int n_bins, uint8_t* present, int64_t* counts,
                     int64_t* tally);
 
+/* ------------------------------------------------------------------ density (heatmap) scan */
+/* DensityScan over point features (idx/iterators/DensityScan.scala:29-49, 201-212): every feature that
+   passed the scan's filters is rendered into a RenderingGrid of width x height pixels over an envelope
+   (geomesa-utils/.../geotools/RenderingGrid.scala:43-49), in FP64 with the JVM's semantics:
+     GridSnap(env, width, height) (geomesa-utils/.../geotools/GridSnap.scala:32-36):
+       dx = (xmax - xmin) / width, dy = (ymax - ymin) / height;
+     GridSnap.i(x) (GridSnap.scala:60-66): -1 when x < xmin || x > xmax, else
+       floor((x - xmin) / dx).toInt (a true division; toInt saturates) clamped to width - 1; j(y) likewise
+       (GridSnap.scala:74-80);
+     RenderingGrid.render(Point, w) (RenderingGrid.scala:43-49): j = j(y); when j != -1, pixel (i, j) += w
+       for every i of translate(x);
+     translate / widen (RenderingGrid.scala:299-330): below xmin, xt = x + 360 * ceil((xmin - x) / 360),
+       nothing when xt > xmax; above xmax, xt = x - 360 * ceil((x - xmax) / 360), nothing when xt < xmin;
+       when xmax - xmin > 360 the grid renders copies: xup = xt - 360 * floor((xt - xmin) / 360),
+       while (xup <= xmax) { i(xup); xup += 360 }; otherwise the one column i(xt).  No multiply-add is fused;
+     the weight (DensityScan.scala:247-259) is 1.0 (EqualWeight, weight = NULL) or a numeric column
+       (WeightByNumber); a null weight is 0.0, which the caller writes.
+   A MultiPoint renders every one of its points with the slot's weight (RenderingGrid.scala:57-64).
+
+   Three places where the dense grid cannot follow the reference's map of pixels, each counted in
+   tally (device int64[3], accumulated into):
+     tally[0]  unrenderable rows, skipped: a null Arrow slot (the reference throws a
+               NullPointerException), a non-finite x or y, |x| > 2^31.  In the reference a NaN ordinate
+               fails both range checks of GridSnap and lands in column or row 0, and an infinite or huge x
+               makes xt NaN or widen's loop endless (xup += 360 is absorbed).  gm_arrow_points_to_columns
+               writes NaN for null slots, so this is also the null rule of x / y columns.  For a MultiPoint
+               a null slot counts once and every such tuple counts;
+     tally[1]  pixel additions whose column came out -1, dropped: xt and xup are rounded and can land an
+               ulp below xmin, where the reference adds to the map key (-1, j), a pixel outside the grid;
+     tally[2]  entries of ids outside [0, n), skipped and never read through.
+
+   The grid description.  workgroups: 0 = the default launch (one resident wave of workgroups), else the
+   launch's workgroup count (raised when a workgroup's counters could otherwise wrap).  path: 0 =
+   automatic, 1 = workgroup-private counters in LDS, flushed with one device atomic per nonzero pixel,
+   2 = one FP64 device atomic per addition.  Both exist so tests reach every path; an unweighted grid never
+   changes with them (integer sums below 2^53 are exact in any order), a weighted one only in the
+   order of its FP64 additions. */
+typedef struct {
+  double xmin, ymin, xmax, ymax;
+  int32_t width, height;
+  int32_t workgroups;
+  int32_t path;
+} gm_density_grid;
+
+/* Renders rows 0 .. n-1 of the device columns x / y (weight: NULL = 1.0) into grid (device, FP64,
+   pixel (i, j) at [j * width + i]).  Selection, at most one of: mask (bit r%64 of word r/64 set = render
+   row r; ceil(n/64) words, as the filter scans write them; bits at and above n are ignored) or ids (n_ids
+   rows to render, in any order; a row named twice renders twice), as a table query returns them.
+   grid and tally are accumulated into and never cleared, and the call is stream-ordered, as
+   gm_z3_histogram: batches, and the grids of several ranks, add.  Columns, mask, ids, grid and tally need
+   8-B alignment; x, y and weight all 16-B aligned take the vector-load kernel.
+   GM_E_INVALID, with a gm_last_error text: a NULL ctx, g, grid or tally; x or y NULL with n > 0; n < 0;
+   width < 1 or height < 1; width * height > 2^31 - 1; xmax <= xmin or ymax <= ymin (the reference's 0/0 for
+   a flat envelope is an accident and is not reproduced); a bound that is not finite or beyond 2^31 in
+   magnitude; xmax - xmin > 360 * 64 (inside this domain widen's loop runs at most
+   floor((xmax - xmin) / 360) + 2 times, which bounds the device loop); mask and ids both given; path
+   outside 0..2, or path 1 for a grid that does not fit (more than 8 passes of 40,704 pixels, 20,352 with
+   weights); workgroups < 0; a misaligned pointer. */
+int gm_density_points(gm_ctx* ctx, const double* x, const double* y, const double* weight, int64_t n,
+                      const uint64_t* mask, const int64_t* ids, int64_t n_ids, const gm_density_grid* g,
+                      double* grid, int64_t* tally);
+/* gm_density_points over the n slots of an Arrow GM_GEOM_POINT or GM_GEOM_MULTIPOINT column (64- or 32-bit
+   ordinates, either axis order), read in place; weight, mask and ids are per slot. */
+int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weight, int64_t n, const uint64_t* mask,
+                     const int64_t* ids, int64_t n_ids, const gm_density_grid* g, double* grid, int64_t* tally);
+/* The grid as the sparse matrix DensityScan.encodeResult writes (DensityScan.scala:95-106): the cells
+   with w != 0.0 into the device arrays i / j / w (cap entries each), ordered by column i, then row j --
+   the order encodeResult groups by.  *n_cells (host) receives the cell count; GM_E_CAPACITY when it
+   exceeds cap (no entry past cap is written; cap = 0 only counts, and i / j / w may then be NULL).
+   Synchronises the context stream.  A pixel whose weights sum to zero is not reported; the reference's
+   map would keep it with 0.0. */
+int gm_density_sparse(gm_ctx* ctx, const double* grid, int32_t width, int32_t height, int64_t cap, int32_t* i,
+                      int32_t* j, double* w, int64_t* n_cells);
+
 /* ------------------------------------------------------------------ synthetic data (bench/tests) */
 /* SplitMix64 keyed by (seed, index): lon U[lon0,lon1), lat U[lat0,lat1), t_ms U[t0,t1).  Each of x, y and
    t_ms is optional (NULL = that column is not generated; the others get the same values either way);
