@@ -6,5 +6,6 @@ libgeomesa_hip.so (include/geomesa_hip.h).  All per-row compute runs in the HIP 
 """
 from .curve import (BinnedTime, CoveredRange, IllegalArgumentException, IndexRange, OverlappingRange,  # noqa: F401
                     TimePeriod, XZ2SFC, XZ3SFC, Z2SFC, Z3SFC)
+from .bin import BinEncoder  # noqa: F401
 
 __version__ = "0.1.0"

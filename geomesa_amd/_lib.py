@@ -94,6 +94,20 @@ class DensityGrid(ctypes.Structure):
                 ("workgroups", ctypes.c_int32), ("path", ctypes.c_int32)]
 
 
+GM_ATTR_INT32, GM_ATTR_INT64, GM_ATTR_FLOAT64, GM_ATTR_UTF8 = 1, 2, 3, 4
+
+
+class AttrColumn(ctypes.Structure):
+    """gm_attr_column: an attribute column gm_bin_track / gm_bin_label read (values, or Utf8 offsets + bytes)."""
+    _fields_ = [("type", ctypes.c_int32), ("reserved", ctypes.c_int32), ("values", ctypes.c_void_p),
+                ("offsets", ctypes.c_void_p), ("validity", ctypes.c_void_p), ("validity_offset", ctypes.c_int64)]
+
+
+class BinOpts(ctypes.Structure):
+    """gm_bin_opts: sort (0 scan order, 1 by BinSorter.compare) and the axis order (0 LonLat, 1 LatLon)."""
+    _fields_ = [("sort", ctypes.c_int32), ("lat_lon", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
 GM_PIP_INDEX_ARRAYS = 8
 GM_PIP_LAYOUT_VERSION = 1
 
@@ -185,6 +199,11 @@ SIGNATURES = {
     "gm_density_points": (cint, [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
     "gm_density_arrow": (cint, [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
     "gm_density_sparse": (cint, [vp, vp, i32, i32, i64, vp, vp, vp, vp]),
+    "gm_bin_track": (cint, [vp, vp, i64, vp]),
+    "gm_bin_label": (cint, [vp, vp, i64, vp]),
+    "gm_bin_points": (cint, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]),
+    "gm_bin_arrow": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]),
+    "gm_bin_sort": (cint, [vp, vp, i64, i32, vp]),
     "gm_gen_points": (cint, [vp, ctypes.c_uint64, i64, i64, d, d, d, d, i64, i64, vp, vp, vp]),
 }
 

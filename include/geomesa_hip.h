@@ -721,6 +721,106 @@ int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weig
 int gm_density_sparse(gm_ctx* ctx, const double* grid, int32_t width, int32_t height, int64_t cap, int32_t* i,
                       int32_t* j, double* w, int64_t* n_cells);
 
+/* ------------------------------------------------------------------ BIN track-record scan */
+/* BinAggregatingScan (idx/iterators/BinAggregatingScan.scala:129-168): every feature that passed the
+   scan's filters becomes little-endian records in one buffer (geomesa-utils/.../bin/
+   BinaryOutputCallback.scala:28-41), 16 B, or 24 B with a label:
+     offset 0   int32   trackId   convertToTrack (geomesa-utils/.../bin/BinaryOutputEncoder.scala:149-150)
+     offset 4   int32   (dtg / 1000).toInt: Long division, truncating toward zero (-1 ms -> 0, -1999 ms
+                        -> -1); toInt keeps the low 32 bits (it wraps); a null date is 0 (:153-154)
+     offset 8   float32 lat       p.getY.toFloat (:295-301), the JVM's d2f: round to nearest even, overflow
+     offset 12  float32 lon       p.getX.toFloat  to +-Inf, float denormals and -0.0 kept; under
+                                  AxisOrder.LatLon lat = x and lon = y (:281-286)
+     offset 16  int64   label     convertToLabel (:156-168), 24-B records only
+   A point feature gives one record (ToValuesPoints[Labels], :326-343); a LineString one per vertex, in vertex
+   order, with the feature's track, label and date (ToValuesLines[Labels], :345-377) or, given a date list,
+   with dates(i) for vertex i, min(vertices, dates) records (ToValuesLinesDates[Labels], :379-419; a null
+   list is empty, :317-320).  Polygons (safeCentroid) are not encoded.
+
+   gm_bin_track / gm_bin_label turn an attribute column into the int32 track / int64 label column the
+   encode reads (a track column is hashed once per table; a BIN query runs many times over it).  A null
+   slot gives 0.  track = hashCode: GM_ATTR_INT32 the value; GM_ATTR_INT64 (int)(v ^ (v >>> 32));
+   GM_ATTR_FLOAT64 the same fold over doubleToLongBits (every NaN is 0x7ff8000000000000 first; -0.0 keeps
+   its sign bit); GM_ATTR_UTF8 String.hashCode, s[0] * 31^(n-1) + ... over UTF-16 code units in wrapping
+   int32, a 4-byte UTF-8 sequence being two surrogate units.  With no track attribute the track is the hash
+   of the feature id string (:247-250): the caller hashes its id column.  label: Number.longValue
+   (GM_ATTR_INT32 sign-extends; GM_ATTR_FLOAT64 is the JVM's saturating d2l, NaN -> 0); GM_ATTR_UTF8 the
+   first 8 UTF-8 bytes, byte i at bits 8i (a multi-byte character may be cut).  UTF-8 input is well
+   formed (Arrow's contract); a malformed or truncated sequence gives an unspecified value and never
+   reads outside the slot's bytes.  Device arrays, naturally aligned; stream-ordered; one lane per slot. */
+#define GM_ATTR_INT32 1
+#define GM_ATTR_INT64 2
+#define GM_ATTR_FLOAT64 3
+#define GM_ATTR_UTF8 4      /* Arrow Utf8: int32 offsets [n + 1] + bytes */
+typedef struct {
+  int32_t type;              /* GM_ATTR_* */
+  int32_t reserved;
+  const void* values;        /* the values; GM_ATTR_UTF8: the bytes */
+  const int32_t* offsets;    /* GM_ATTR_UTF8 only: slot i is bytes [offsets[i], offsets[i + 1]) */
+  const uint8_t* validity;   /* NULL = no nulls */
+  int64_t validity_offset;
+} gm_attr_column;
+
+int gm_bin_track(gm_ctx* ctx, const gm_attr_column* col, int64_t n, int32_t* track);
+int gm_bin_label(gm_ctx* ctx, const gm_attr_column* col, int64_t n, int64_t* label);
+
+typedef struct {
+  int32_t sort;        /* 0: scan order; 1: by BinSorter.compare, stable */
+  int32_t lat_lon;     /* 0: AxisOrder.LonLat (the default); 1: LatLon */
+  int32_t reserved[2];
+} gm_bin_opts;
+
+/* Encodes rows 0 .. n-1 of the device columns x / y / t_ms (NULL: date 0) / track / label (NULL: 16-B
+   records) into out (device, cap records).  Selection as gm_density_points: at most one of mask (bits at
+   and above n are ignored) or ids (n_ids rows, in any order, a row named twice encoded twice; entries
+   outside [0, n) are skipped and counted).
+   Order.  Without sort: ascending row (no selection, mask) or the order of ids -- a table query returns its
+   ids in table order, the reference's scan order -- and vertex order within a line.  With sort: by
+   BinSorter.compare (idx/utils/bin/BinSorter.scala:38-79), the int32 at offset 4 compared signed, stable.
+   The reference's quickSort (:155) leaves the order among equal seconds unspecified, so any tie order is
+   its; the stable one makes the result fixed, and the stable sort of left ++ right, both sorted, is byte
+   for byte BinSorter.mergeSort(left, right) (:115-145), which takes from left on ties.
+   tally (device int64[3], accumulated into):
+     tally[0]  records not written because the geometry is null (the reference throws a
+               NullPointerException) or an ordinate is NaN (the float payload of a NaN after d2f is not
+               portable); gm_arrow_points_to_columns writes NaN for null slots, so this is also the null
+               rule of x / y columns.  +-Inf and values outside the float range are encoded;
+     tally[1]  entries of ids outside [0, n), skipped and never read through;
+     tally[2]  selected line slots whose date list length differs from the vertex count (the reference
+               logs a warning and uses the minimum; so does this).
+   *n_records (host) receives the full record count; GM_E_CAPACITY when it exceeds cap, and then out is
+   not written; cap = 0 with out = NULL only counts.  Nothing past cap records is ever written; what out
+   holds past *n_records records is unspecified.  The call synchronises the context stream for that
+   readback, as gm_density_sparse.  Without a mask, and with room for every selected row (cap >= n, or
+   n_ids), the records are first written in one pass on the assumption that every selected row gives one;
+   a null geometry, a NaN or a bad id among them makes the count -> scan -> write passes run after it,
+   and the result is the same.  Pointers need 8-B alignment; x, y, t_ms and label all 16-B aligned take
+   the vector-load kernel, a 16-B aligned out 16-B stores.
+   GM_E_INVALID, with a gm_last_error text: a NULL ctx, o, tally or n_records; x, y or track NULL with
+   n > 0 (without a track attribute, hash the feature ids with gm_bin_track); n, n_ids or cap negative; a
+   NULL out with cap > 0; mask and ids both given; sort or lat_lon outside 0..1; more than 2^32 - 1
+   records with sort; a misaligned pointer. */
+int gm_bin_points(gm_ctx* ctx, const double* x, const double* y, const int64_t* t_ms, const int32_t* track,
+                  const int64_t* label, int64_t n, const uint64_t* mask, const int64_t* ids, int64_t n_ids,
+                  const gm_bin_opts* o, uint8_t* out, int64_t cap, int64_t* n_records, int64_t* tally);
+/* gm_bin_points over the n slots of an Arrow GM_GEOM_POINT or GM_GEOM_LINESTRING column (64- or 32-bit
+   ordinates, either axis order), read in place; dtg (NULL, or a null slot: date 0), track, label, mask and
+   ids are per slot.  date_off / dates (both NULL: the slot's single date) give a line column its date
+   list: slot i's dates are dates[date_off[i] .. date_off[i + 1]) (a null element is date 0; a null list
+   has no entries).  Also GM_E_INVALID: another geometry type; exactly one of date_off / dates; dates with
+   a GM_GEOM_POINT column.  A null line slot counts once in tally[0], a NaN vertex once each.  A line
+   column takes a second readback (the vertices its selection asks for). */
+int gm_bin_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* dtg, const int32_t* date_off,
+                 const gm_time_column* dates, const int32_t* track, const int64_t* label, int64_t n,
+                 const uint64_t* mask, const int64_t* ids, int64_t n_ids, const gm_bin_opts* o, uint8_t* out,
+                 int64_t cap, int64_t* n_records, int64_t* tally);
+/* The stable sort by BinSorter.compare of n_records records of record_bytes (16 or 24) each, in (device)
+   into out (device, another buffer).  A concatenation of sorted batches comes out as their merge
+   (BinSorter.mergeSort, BinSorter.scala:85-145), so the batches of several ranks combine through it.
+   GM_E_INVALID: record_bytes other than 16 / 24; n_records negative or above 2^32 - 1; NULL, misaligned or
+   aliased buffers.  Device temporaries: 24 B per record plus gm_sort_keys's. */
+int gm_bin_sort(gm_ctx* ctx, const uint8_t* in, int64_t n_records, int32_t record_bytes, uint8_t* out);
+
 /* ------------------------------------------------------------------ synthetic data (bench/tests) */
 /* SplitMix64 keyed by (seed, index): lon U[lon0,lon1), lat U[lat0,lat1), t_ms U[t0,t1).  Each of x, y and
    t_ms is optional (NULL = that column is not generated; the others get the same values either way);
