@@ -15,27 +15,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
+from .curve import _dev_col, _selection
 
 # a decoded record (BinaryOutputEncoder.EncodedValues, BinaryOutputEncoder.scala:107): dtg in ms, label -1
 # for 16-B records
 DECODED = np.dtype([("track", "<i4"), ("dtg", "<i8"), ("lat", "<f4"), ("lon", "<f4"), ("label", "<i8")])
 RECORD16 = np.dtype([("track", "<i4"), ("secs", "<i4"), ("lat", "<f4"), ("lon", "<f4")])
 RECORD24 = np.dtype([("track", "<i4"), ("secs", "<i4"), ("lat", "<f4"), ("lon", "<f4"), ("label", "<i8")])
-
-
-def _col(a, dtype, dev):
-    """A contiguous device tensor of `dtype` for a column (no copy if already one); None passes through."""
-    import torch
-    if a is None:
-        return None
-    if not isinstance(a, torch.Tensor):
-        a = np.ascontiguousarray(np.asarray(a))
-        a = torch.from_numpy(a if a.flags.writeable else a.copy())   # torch wants a writable array
-    if a.device != dev:
-        a = a.to(dev)
-    if a.dtype != dtype:
-        a = a.to(dtype)
-    return a.contiguous()
 
 
 def _utf8_column(strings):
@@ -86,9 +72,9 @@ class BinEncoder:
         if isinstance(column, (list, tuple)) and all(isinstance(s, (str, type(None))) for s in column):
             column = _utf8_column(column)
         if isinstance(column, tuple):
-            off = _col(column[0], torch.int32, dev)
-            data = _col(column[1], torch.uint8, dev)
-            valid = _col(column[2], torch.uint8, dev) if len(column) > 2 and column[2] is not None else None
+            off = _dev_col(column[0], torch.int32, dev)
+            data = _dev_col(column[1], torch.uint8, dev)
+            valid = _dev_col(column[2], torch.uint8, dev) if len(column) > 2 and column[2] is not None else None
             voff = int(column[3]) if len(column) > 3 else 0
             n = off.numel() - 1
             if data.numel() == 0:
@@ -132,29 +118,14 @@ class BinEncoder:
     def _opts(self):
         return _lib.BinOpts(int(self.sorted), int(self.lat_lon))
 
-    def _selection(self, n, mask, ids):
-        import torch
-        from .density import _pack_mask
-        if mask is not None and ids is not None:
-            raise ValueError("give a mask or ids, not both")
-        if mask is not None:
-            mask = _pack_mask(mask, n, self._dev)
-        n_ids = 0
-        if ids is not None:
-            ids = _col(ids, torch.int64, self._dev)
-            n_ids = ids.numel()
-            if n_ids == 0:   # an empty selection still is one: a valid pointer for it
-                ids = torch.zeros(1, dtype=torch.int64, device=self._dev)
-        return mask, ids, n_ids
-
     def _columns(self, n, track, label):
         import torch
-        track = _col(track, torch.int32, self._dev)
+        track = _dev_col(track, torch.int32, self._dev)
         if track is None or track.numel() != n:
             raise ValueError("track must have one entry per row (track_of hashes an attribute or id column)")
         if self.label != (label is not None):
             raise ValueError("a label column goes with BinEncoder(label=True), and only with it")
-        label = _col(label, torch.int64, self._dev)
+        label = _dev_col(label, torch.int64, self._dev)
         if label is not None and label.numel() != n:
             raise ValueError("label must have one entry per row")
         return track, label
@@ -176,14 +147,14 @@ class BinEncoder:
     def encode(self, x, y, t_ms, track, label=None, mask=None, ids=None):
         """ToValuesPoints[Labels] over rows of x / y / t_ms (None: date 0) / track / label columns."""
         import torch
-        x = _col(x, torch.float64, self._dev)
-        y = _col(y, torch.float64, self._dev)
-        t = _col(t_ms, torch.int64, self._dev)
+        x = _dev_col(x, torch.float64, self._dev)
+        y = _dev_col(y, torch.float64, self._dev)
+        t = _dev_col(t_ms, torch.int64, self._dev)
         n = x.numel()
         if y.numel() != n or (t is not None and t.numel() != n):
             raise ValueError("x, y and t_ms must have one entry per row")
         track, label = self._columns(n, track, label)
-        mask, ids, n_ids = self._selection(n, mask, ids)
+        mask, ids, n_ids = _selection(n, mask, ids, self._dev)
         ctx = _lib.context(self._device)
         o = self._opts()
 
@@ -206,11 +177,11 @@ class BinEncoder:
         n = col.n
         t = _as_time(dtg)
         track, label = self._columns(n, track, label)
-        mask, ids, n_ids = self._selection(n, mask, ids)
+        mask, ids, n_ids = _selection(n, mask, ids, self._dev)
         d_off = d_ms = dc = None
         if dates is not None:
-            d_off = _col(dates[0], torch.int32, self._dev)
-            d_ms = _col(dates[1], torch.int64, self._dev)
+            d_off = _dev_col(dates[0], torch.int32, self._dev)
+            d_ms = _dev_col(dates[1], torch.int64, self._dev)
             if d_off.numel() != n + 1:
                 raise ValueError("dates' offsets need one entry per slot and one more")
             if d_ms.numel() == 0:
@@ -233,7 +204,7 @@ class BinEncoder:
     def sort(self, records):
         """The records ordered by BinSorter.compare, stably (a new tensor)."""
         import torch
-        records = _col(records, torch.uint8, self._dev)
+        records = _dev_col(records, torch.uint8, self._dev)
         if records.numel() % self.record_bytes:
             raise ValueError("records are %d bytes each" % self.record_bytes)
         ctx = _lib.context(self._device)
@@ -246,7 +217,7 @@ class BinEncoder:
         """BinSorter.mergeSort over sorted batches (BinSorter.scala:85-145): their concatenation, sorted
         stably, so ties come from the earlier chunk first."""
         import torch
-        chunks = [_col(c, torch.uint8, self._dev) for c in chunks]
+        chunks = [_dev_col(c, torch.uint8, self._dev) for c in chunks]
         if not chunks:
             return torch.empty(0, dtype=torch.uint8, device=self._dev)
         return self.sort(torch.cat(chunks))

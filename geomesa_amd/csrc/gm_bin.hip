@@ -15,8 +15,9 @@
 // (k_bin_slots: min(vertices, dates) per selected slot), a scan of those counts, and find a candidate's
 // slot again by binary search over the scanned offsets, so a slot of any length is spread over as many
 // lanes as it has vertices and still comes out in vertex order.  From there both run the count ->
-// launch_excl_scan -> write pipeline of gm_scan.hpp over blocks of BROWS candidates: k_bin<false> counts
-// the records of each block (a candidate with a null geometry or a NaN ordinate writes none) and takes
+// scan -> write pipeline of gm_scan.hpp (CountScan) over blocks of BROWS candidates: k_bin<false> counts
+// the records of each block (a candidate with a null geometry or a NaN ordinate writes none; the selection
+// is gm_scan.hpp's RowSel, resolved per entry by sel_row, per pair of rows by mask_pair) and takes
 // the tallies, k_bin<true> reads the rows again, ranks them with wave ballots in candidate order and
 // writes.  Without a mask that pipeline is the second attempt: the records are first written in one pass
 // at their candidates' own positions, which is the result whenever every candidate wrote one (bin_encode).
@@ -41,13 +42,11 @@ constexpr int BPAIRS = 4;                     // pair steps per lane
 constexpr int BROWS = BTPB * BPAIRS * 2;      // candidates per block (2048)
 constexpr int BWAVES = BTPB / 64;
 
-enum : int { BSEL_NONE = 0, BSEL_MASK = 1, BSEL_IDS = 2 };
 enum : int { BSRC_COLS = 0, BSRC_POINT = 1, BSRC_LINE = 2 };
 
 struct BinArgs {
-  int64_t n;        // rows (columns) or slots (Arrow)
-  int64_t units;    // entries of the selection: n, or the entries of ids
-  int64_t ncand;    // candidate records: units (points), the scanned slot counts' total (lines)
+  RowSel sel;       // over the rows (columns) or slots (Arrow)
+  int64_t ncand;    // candidate records: sel.units (points), the scanned slot counts' total (lines)
   int64_t cap;      // records `out` holds
   const double* x;
   const double* y;
@@ -62,9 +61,7 @@ struct BinArgs {
   int64_t dates_voff;
   const int32_t* track;
   const int64_t* label;
-  const uint64_t* mask;
-  const int64_t* ids;
-  const int64_t* cand_off;      // line: units + 1 scanned candidate counts
+  const int64_t* cand_off;      // line: sel.units + 1 scanned candidate counts
   unsigned long long* holes;    // the direct write: candidates that wrote no record
   int32_t lat_lon;
   int32_t out16;                // `out` is 16-B aligned
@@ -103,19 +100,12 @@ template <int SEL>
 __global__ __launch_bounds__(256) void k_bin_slots(BinArgs a, int32_t* __restrict__ cand,
                                                    unsigned long long* __restrict__ tally) {
   const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (u >= a.units) return;
-  int64_t r = u;
-  bool sel = true;
-  if (SEL == BSEL_MASK) sel = (a.mask[u >> 6] >> (u & 63)) & 1ull;
-  if (SEL == BSEL_IDS) {
-    r = a.ids[u];
-    if ((uint64_t)r >= (uint64_t)a.n) {
-      atomicAdd(&tally[1], 1ull);
-      sel = false;
-    }
-  }
+  if (u >= a.sel.units) return;
+  int64_t r;
+  const int sel = sel_row<SEL>(a.sel, u, r);
+  if (sel < 0) atomicAdd(&tally[1], 1ull);
   int32_t m = 0;
-  if (sel) {
+  if (sel > 0) {
     if (!arrow_valid(a.pts.valid, a.pts.voff, r)) {
       atomicAdd(&tally[0], 1ull);   // the reference throws a NullPointerException
     } else {
@@ -175,23 +165,13 @@ __global__ __launch_bounds__(BTPB) void k_bin(BinArgs a, int32_t* __restrict__ c
     int64_t rr = c, i = 0;
     double x, y;
     if (SRC == BSRC_LINE) {
-      const int64_t u = [&] {
-        int64_t lo = 0, hi = a.units;
-        while (lo < hi) {
-          const int64_t m = (lo + hi) >> 1;
-          if (a.cand_off[m] <= c) lo = m + 1; else hi = m;
-        }
-        return lo - 1;
-      }();
+      const int64_t u = offset_slot(a.cand_off, a.sel.units, c);
       i = c - a.cand_off[u];
-      rr = SEL == BSEL_IDS ? a.ids[u] : u;
+      rr = SEL == SEL_IDS ? a.sel.ids[u] : u;
       arrow_tuple<F32>(a.pts.c, (int64_t)a.o0[rr] + i, a.pts.flip, x, y);
     } else {
-      if (SEL == BSEL_MASK && !((a.mask[c >> 6] >> (c & 63)) & 1ull)) return;
-      if (SEL == BSEL_IDS) {
-        rr = a.ids[c];
-        if ((uint64_t)rr >= (uint64_t)a.n) { ++bad; return; }
-      }
+      const int k = sel_row<SEL>(a.sel, c, rr);
+      if (k <= 0) { bad += k < 0; return; }
       if (SRC == BSRC_COLS) {
         x = a.x[rr];
         y = a.y[rr];
@@ -210,11 +190,7 @@ __global__ __launch_bounds__(BTPB) void k_bin(BinArgs a, int32_t* __restrict__ c
     r[u][0].ok = r[u][1].ok = false;
     if (VEC && c + 1 < a.ncand) {   // rows c and c + 1 of 16-B aligned columns, both in mask word c >> 6
       bool se = true, so = true;
-      if (SEL == BSEL_MASK) {
-        const uint64_t w = a.mask[c >> 6] >> (c & 63);
-        se = w & 1ull;
-        so = (w >> 1) & 1ull;
-      }
+      if (SEL == SEL_MASK) mask_pair(a.sel.mask[p >> 5], p, se, so);
       if (se || so) {
         const dv2 xv = ld_stream((const dv2*)a.x + p), yv = ld_stream((const dv2*)a.y + p);
         if (se) keep(r[u][0], xv.x, yv.x);
@@ -382,15 +358,13 @@ int bin_check(const char* who, gm_ctx* ctx, int64_t n, const int32_t* track, con
   if (!tally) return bin_fail(who, "NULL tally");
   if (!n_records) return bin_fail(who, "NULL n_records");
   if (n < 0) return bin_fail(who, "negative row count");
-  if (ids && n_ids < 0) return bin_fail(who, "negative id count");
   if (cap < 0) return bin_fail(who, "negative capacity");
   if (cap > 0 && !out) return bin_fail(who, "NULL output with a capacity");
-  if (mask && ids) return bin_fail(who, "mask and ids are exclusive");
+  if (const char* why = sel_check(mask, ids, n_ids)) return bin_fail(who, why);
   if (o->sort < 0 || o->sort > 1) return bin_fail(who, "sort must be 0 or 1");
   if (o->lat_lon < 0 || o->lat_lon > 1) return bin_fail(who, "lat_lon must be 0 or 1");
   if (!track && n > 0) return bin_fail(who, "NULL track column (hash the feature ids with gm_bin_track)");
-  if (!aligned_to<8>(track) || !aligned_to<8>(label) || !aligned_to<8>(mask) || !aligned_to<8>(ids) ||
-      !aligned_to<8>(out) || !aligned_to<8>(tally))
+  if (!aligned_to<8>(track) || !aligned_to<8>(label) || !aligned_to<8>(out) || !aligned_to<8>(tally))
     return bin_fail(who, "columns and outputs need 8-B alignment");
   return GM_OK;
 }
@@ -399,48 +373,36 @@ int bin_encode(const char* who, gm_ctx* ctx, int src, bool f32, BinArgs a, const
                int64_t* n_records, int64_t* tally) {
   GM_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int sel = a.ids ? BSEL_IDS : (a.mask ? BSEL_MASK : BSEL_NONE);
+  const int sel = sel_of(a.sel);
   const bool label = a.label != nullptr;
   const int rb = label ? 24 : 16;
   a.lat_lon = o->lat_lon;
   *n_records = 0;
-  if (a.units == 0) return GM_OK;
+  if (a.sel.units == 0) return GM_OK;
   DevTemps tmp(s);
-  auto read_total = [&](const int64_t* dev, int64_t* host) -> int {
-    GM_HIP(hipMemcpyAsync(ctx->h_pinned, dev, 8, hipMemcpyDeviceToHost, s));
-    GM_HIP(hipStreamSynchronize(s));
-    *host = ctx->h_pinned[0];
-    return GM_OK;
-  };
-  a.ncand = a.units;
+  a.ncand = a.sel.units;
   if (src == BSRC_LINE) {
-    int32_t* cand;
-    int64_t *cand_off, *partials;
-    int rc = tmp.alloc_async((size_t)a.units * 4, &cand);
-    if (!rc) rc = tmp.alloc_async((size_t)(a.units + 1) * 8, &cand_off);
-    if (!rc) rc = tmp.alloc_async((size_t)scan_partials_len(a.units) * 8, &partials);
+    CountScan slots;   // one count per entry of the selection
+    int rc = slots.alloc(tmp, a.sel.units);
     if (rc) return rc;
-    rc = with_value<BSEL_NONE, BSEL_MASK, BSEL_IDS>(sel, [&](auto E) -> int {
-      hipLaunchKernelGGL(k_bin_slots<E()>, dim3(grid_for(a.units, 256)), dim3(256), 0, s, a, cand,
+    rc = with_value<SEL_NONE, SEL_MASK, SEL_IDS>(sel, [&](auto E) -> int {
+      hipLaunchKernelGGL(k_bin_slots<E()>, dim3(grid_for(a.sel.units, 256)), dim3(256), 0, s, a, slots.counts,
                          (unsigned long long*)tally);
       GM_CHECK_LAUNCH();
       return GM_OK;
     });
+    if (!rc) rc = slots.scan(ctx);
+    if (!rc) rc = slots.total(ctx, &a.ncand);
     if (rc) return rc;
-    launch_excl_scan(s, (const int32_t*)cand, a.units, cand_off, partials, cand_off + a.units);
-    GM_CHECK_LAUNCH();
-    rc = read_total(cand_off + a.units, &a.ncand);
-    if (rc) return rc;
-    a.cand_off = cand_off;
+    a.cand_off = slots.offsets;
     if (a.ncand == 0) return GM_OK;
   }
   const int64_t nb = (a.ncand + BROWS - 1) / BROWS;
   if (nb > 2147483647LL) return bin_fail(who, "more than 2^31 - 1 blocks of candidate records");
-  const bool vec = src == BSRC_COLS && sel != BSEL_IDS && aligned16(a.x) && aligned16(a.y) && aligned16(a.dtg) &&
+  const bool vec = src == BSRC_COLS && sel != SEL_IDS && aligned16(a.x) && aligned16(a.y) && aligned16(a.dtg) &&
                    aligned16(a.label);
   const int64_t user_cap = a.cap;
-  int32_t* counts = nullptr;
-  int64_t* offs = nullptr;
+  CountScan blocks;   // one count per block of candidates
   uint8_t* dst = out;
   // with sort the records are written to a temporary of `recs` records, then sorted into out
   auto stage = [&](int64_t recs) -> int {
@@ -456,22 +418,22 @@ int bin_encode(const char* who, gm_ctx* ctx, int src, bool f32, BinArgs a, const
   // mask was resolved per slot
   auto launch = [&](auto W, auto D) -> int {
     auto go = [&](auto kern) -> int {
-      hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(BTPB), 0, s, a, counts, (const int64_t*)offs, dst,
-                         (unsigned long long*)tally);
+      hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(BTPB), 0, s, a, blocks.counts, (const int64_t*)blocks.offsets,
+                         dst, (unsigned long long*)tally);
       GM_CHECK_LAUNCH();
       return GM_OK;
     };
     return with_value<BSRC_COLS, BSRC_POINT, BSRC_LINE>(src, [&](auto S) {
-      return with_value<BSEL_NONE, BSEL_MASK, BSEL_IDS>(sel, [&](auto E) {
+      return with_value<SEL_NONE, SEL_MASK, SEL_IDS>(sel, [&](auto E) {
         return with_flags([&](auto L, auto V, auto F) {
           constexpr bool WR = decltype(W)::value;
           constexpr bool DR = decltype(D)::value;
           if constexpr (S() == BSRC_COLS)
-            return go(k_bin<WR, BSRC_COLS, E(), WR && L(), V() && E() != BSEL_IDS, false, DR && E() != BSEL_MASK>);
+            return go(k_bin<WR, BSRC_COLS, E(), WR && L(), V() && E() != SEL_IDS, false, DR && E() != SEL_MASK>);
           else if constexpr (S() == BSRC_LINE)
-            return go(k_bin<WR, BSRC_LINE, E() == BSEL_IDS ? BSEL_IDS : BSEL_NONE, WR && L(), false, F(), DR>);
+            return go(k_bin<WR, BSRC_LINE, E() == SEL_IDS ? SEL_IDS : SEL_NONE, WR && L(), false, F(), DR>);
           else
-            return go(k_bin<WR, BSRC_POINT, E(), WR && L(), false, F(), DR && E() != BSEL_MASK>);
+            return go(k_bin<WR, BSRC_POINT, E(), WR && L(), false, F(), DR && E() != SEL_MASK>);
         }, label, vec, f32);
       });
     });
@@ -482,31 +444,25 @@ int bin_encode(const char* who, gm_ctx* ctx, int src, bool f32, BinArgs a, const
   // row where count + write take 60 (7.6 ms per 1B 16-B records against 10.6: tools/bin_scan_probe.py's
   // NaN-row leg runs both, 18.3 ms).  Any, and the count -> scan -> write pipeline below runs over the
   // same rows and writes the buffer again.
-  if ((src == BSRC_LINE || sel != BSEL_MASK) && a.ncand <= user_cap && !(o->sort && a.ncand > (int64_t)UINT32_MAX)) {
+  if ((src == BSRC_LINE || sel != SEL_MASK) && a.ncand <= user_cap && !(o->sort && a.ncand > (int64_t)UINT32_MAX)) {
     int rc = tmp.alloc_async(8, &a.holes);
     if (rc) return rc;
     GM_HIP(hipMemsetAsync(a.holes, 0, 8, s));
     rc = stage(a.ncand);
     if (!rc) rc = launch(Bool<true>{}, Bool<true>{});
     int64_t holes = 0;
-    if (!rc) rc = read_total((const int64_t*)a.holes, &holes);
+    if (!rc) rc = read_i64(ctx, a.holes, &holes);
     if (rc) return rc;
     if (holes == 0) {
       *n_records = a.ncand;
       return o->sort ? bin_sort(ctx, dst, a.ncand, rb, out) : GM_OK;
     }
   }
-  int64_t* partials;
-  int rc = tmp.alloc_async((size_t)nb * 4, &counts);
-  if (!rc) rc = tmp.alloc_async((size_t)(nb + 1) * 8, &offs);
-  if (!rc) rc = tmp.alloc_async((size_t)scan_partials_len(nb) * 8, &partials);
-  if (rc) return rc;
-  rc = launch(Bool<false>{}, Bool<false>{});
-  if (rc) return rc;
-  launch_excl_scan(s, (const int32_t*)counts, nb, offs, partials, offs + nb);
-  GM_CHECK_LAUNCH();
   int64_t total = 0;
-  rc = read_total(offs + nb, &total);
+  int rc = blocks.alloc(tmp, nb);
+  if (!rc) rc = launch(Bool<false>{}, Bool<false>{});
+  if (!rc) rc = blocks.scan(ctx);
+  if (!rc) rc = blocks.total(ctx, &total);
   if (rc) return rc;
   *n_records = total;
   if (total > user_cap) return GM_E_CAPACITY;
@@ -632,16 +588,13 @@ int gm_bin_points(gm_ctx* ctx, const double* x, const double* y, const int64_t* 
   if (!aligned_to<8>(x) || !aligned_to<8>(y) || !aligned_to<8>(t_ms))
     return bin_fail(who, "x, y and t_ms need 8-B alignment");
   BinArgs a{};
-  a.n = n;
-  a.units = ids ? n_ids : n;
+  a.sel = row_sel(n, mask, ids, n_ids);
   a.cap = cap;
   a.x = x;
   a.y = y;
   a.dtg = t_ms;
   a.track = track;
   a.label = label;
-  a.mask = mask;
-  a.ids = ids;
   return bin_encode(who, ctx, BSRC_COLS, false, a, o, out, n_records, tally);
 }
 
@@ -662,13 +615,10 @@ int gm_bin_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* 
       (geom && (!aligned_to<8>(geom->coords) || !aligned_to<4>(geom->offsets[0]))))
     return bin_fail(who, "ordinates and dates need 8-B alignment, List offsets 4-B");
   BinArgs a{};
-  a.n = n;
-  a.units = ids ? n_ids : n;
+  a.sel = row_sel(n, mask, ids, n_ids);
   a.cap = cap;
   a.track = track;
   a.label = label;
-  a.mask = mask;
-  a.ids = ids;
   int src = BSRC_POINT;
   bool f32 = false;
   if (n > 0) {

@@ -21,6 +21,8 @@
 // path with the grid: ids take LDS counters only when one pass holds the grid (every pass gathers again);
 // a mask's popcount is taken on the device and both forms are enqueued, each leaving at once unless the
 // count falls on its side of DENS_PASS_SHARE x (passes - 1) x n (the call stays stream-ordered).
+// The selection is gm_scan.hpp's RowSel (sel_row per entry, mask_pair per pair of rows; sel_check for the
+// entry points' shared argument errors); gm_density_sparse's count -> scan -> total is its CountScan.
 #include <algorithm>
 #include <cmath>
 
@@ -40,12 +42,10 @@ constexpr double DENS_PASS_SHARE = 0.08;   // selected share of the rows at whic
 constexpr uint32_t DENS_THREAD_DRAIN = 1u << 19;
 static_assert((uint64_t)DTPB * DENS_THREAD_DRAIN < (1ull << 32), "thread drain: a counter could wrap");
 
-enum : int { SEL_NONE = 0, SEL_MASK = 1, SEL_IDS = 2 };
 enum : int { SRC_COLS = 0, SRC_POINT = 1, SRC_MULTI = 2 };
 
 struct DensArgs {
-  int64_t n;        // rows (columns) or slots (Arrow)
-  int64_t n_sel;    // SEL_IDS: entries of ids
+  RowSel sel;       // over the rows (columns) or slots (Arrow)
   double xmin, ymin, xmax, ymax;
   double dx, dy;    // GridSnap.scala:32-33
   double rdx, rdy;  // fl(1 / dx), fl(1 / dy): the quotient's estimate (grid_snap)
@@ -66,8 +66,6 @@ struct DensSrc {
   const double* w;      // per row / per slot; unread when unweighted
   ArrowPts pts;
   const int32_t* o0;    // multipoint: slot -> tuples
-  const uint64_t* mask;
-  const int64_t* ids;
 };
 
 // GridSnap.i / GridSnap.j (GridSnap.scala:60-80): -1 outside [lo, hi], else floor((v - lo) / d).toInt
@@ -117,7 +115,7 @@ __device__ __forceinline__ void render_point(double x, double y, const DensArgs&
 }
 
 // SRC: x / y columns, an Arrow point column or an Arrow multipoint column (F32: Float4 ordinates).
-// SEL: every row, the rows of a mask, or the rows ids names.  LDS: the pass's pixel rows live in LDS
+// SEL: every row, the rows of a mask, or the rows ids names (gm_scan.hpp's RowSel).  LDS: the pass's pixel rows live in LDS
 // (uint32 counters, or FP64 cells when WEIGHTED) and are flushed at the end; else every addition is a
 // device atomic.  VEC (columns, no ids): 16-B pair loads, software-pipelined as k_z3_hist_lds.
 //
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(DTPB) void k_density(DensSrc s, DensArgs a, double*
   auto point = [&](double x, double y, double w) {
     render_point(x, y, a, skip, drop, [&](int i, int j) { emit(i, j, w); });
   };
-  auto row = [&](int64_t r) {   // 0 <= r < a.n
+  auto row = [&](int64_t r) {   // 0 <= r < a.sel.n
     if (SRC == SRC_COLS) {
       point(s.x[r], s.y[r], WEIGHTED ? s.w[r] : 1.0);
     } else {
@@ -183,18 +181,12 @@ __global__ __launch_bounds__(DTPB) void k_density(DensSrc s, DensArgs a, double*
       }
     }
   };
-  auto selected = [&](int64_t r) { return SEL != SEL_MASK || ((s.mask[r >> 6] >> (r & 63)) & 1ull); };
   const int64_t stride = (int64_t)gridDim.x * DTPB;
-  if (SEL == SEL_IDS) {
-    for (int64_t k = (int64_t)blockIdx.x * DTPB + threadIdx.x; k < a.n_sel; k += stride) {
-      const int64_t r = s.ids[k];
-      if ((uint64_t)r >= (uint64_t)a.n) ++bad; else row(r);
-    }
-  } else if (VEC) {
+  if constexpr (VEC) {
     const dv2* x2 = (const dv2*)s.x;
     const dv2* y2 = (const dv2*)s.y;
     const dv2* w2 = (const dv2*)s.w;
-    const int64_t np = a.n >> 1;
+    const int64_t np = a.sel.n >> 1;
     constexpr int HU = 2;
     dv2 xa[HU], ya[HU], wa[HU];
     uint64_t ma[HU];
@@ -205,7 +197,7 @@ __global__ __launch_bounds__(DTPB) void k_density(DensSrc s, DensArgs a, double*
       xv = ld_stream(&x2[qc]);
       yv = ld_stream(&y2[qc]);
       if (WEIGHTED) wv = ld_stream(&w2[qc]);
-      if (SEL == SEL_MASK) mv = s.mask[qc >> 5];
+      if (SEL == SEL_MASK) mv = a.sel.mask[qc >> 5];
     };
     const int64_t p0 = (int64_t)blockIdx.x * DTPB;
     if (p0 < np) {
@@ -222,17 +214,22 @@ __global__ __launch_bounds__(DTPB) void k_density(DensSrc s, DensArgs a, double*
       for (int u = 0; u < HU; ++u) {
         const int64_t q = p + u * stride;
         if (q < np) {
-          const int b = (int)((2 * q) & 63);
-          if (SEL != SEL_MASK || ((ma[u] >> b) & 1ull)) point(xa[u].x, ya[u].x, WEIGHTED ? wa[u].x : 1.0);
-          if (SEL != SEL_MASK || ((ma[u] >> (b + 1)) & 1ull)) point(xa[u].y, ya[u].y, WEIGHTED ? wa[u].y : 1.0);
+          bool se = true, so = true;
+          if (SEL == SEL_MASK) mask_pair(ma[u], q, se, so);
+          if (se) point(xa[u].x, ya[u].x, WEIGHTED ? wa[u].x : 1.0);
+          if (so) point(xa[u].y, ya[u].y, WEIGHTED ? wa[u].y : 1.0);
         }
         xa[u] = xb[u]; ya[u] = yb[u]; wa[u] = wb[u]; ma[u] = mb[u];
       }
     }
-    if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0 && selected(a.n - 1)) row(a.n - 1);
+    if ((a.sel.n & 1) && blockIdx.x == 0 && threadIdx.x == 0 && (SEL != SEL_MASK || mask_bit(a.sel.mask, a.sel.n - 1)))
+      row(a.sel.n - 1);
   } else {
-    for (int64_t r = (int64_t)blockIdx.x * DTPB + threadIdx.x; r < a.n; r += stride)
-      if (selected(r)) row(r);
+    for (int64_t u = (int64_t)blockIdx.x * DTPB + threadIdx.x; u < a.sel.units; u += stride) {
+      int64_t r;
+      const int k = sel_row<SEL>(a.sel, u, r);
+      if (k > 0) row(r); else if (k < 0) ++bad;
+    }
   }
   if (skip) atomicAdd(&s_tally[0], (unsigned long long)skip);
   if (drop) atomicAdd(&s_tally[1], (unsigned long long)drop);
@@ -276,11 +273,10 @@ inline int dens_passes(const gm_density_grid* g, bool weighted) {
   return std::min((g->height + rows - 1) / rows, DENS_MAX_PASSES + 1);
 }
 
-int launch_density(gm_ctx* ctx, int src, bool f32, DensSrc s, int64_t n, int64_t n_ids, const gm_density_grid* g,
-                   double* grid, int64_t* tally) {
+int launch_density(gm_ctx* ctx, int src, bool f32, DensSrc s, RowSel rows, const gm_density_grid* g, double* grid,
+                   int64_t* tally) {
   DensArgs a;
-  a.n = n;
-  a.n_sel = n_ids;
+  a.sel = rows;
   a.xmin = g->xmin; a.ymin = g->ymin; a.xmax = g->xmax; a.ymax = g->ymax;
   a.width = g->width; a.height = g->height;
   a.dx = (g->xmax - g->xmin) / g->width;
@@ -290,9 +286,9 @@ int launch_density(gm_ctx* ctx, int src, bool f32, DensSrc s, int64_t n, int64_t
   a.wide = g->xmax - g->xmin > 360.0;
   a.copies = (int)std::floor((g->xmax - g->xmin) / 360.0) + 2;
   const bool weighted = s.w != nullptr;
-  const int sel = s.ids ? SEL_IDS : (s.mask ? SEL_MASK : SEL_NONE);
+  const int sel = sel_of(rows);
   const int fit = dens_passes(g, weighted);
-  const int64_t units = sel == SEL_IDS ? n_ids : n;
+  const int64_t n = a.sel.n, units = a.sel.units;
   // the automatic path (see the head of this file); gated: decided on the device by the mask's popcount
   const bool lds = g->path == 1 || (g->path == 0 && fit <= DENS_MAX_PASSES && (sel != SEL_IDS || fit == 1));
   const bool gated = g->path == 0 && sel == SEL_MASK && fit > 1 && fit <= DENS_MAX_PASSES;
@@ -305,7 +301,7 @@ int launch_density(gm_ctx* ctx, int src, bool f32, DensSrc s, int64_t n, int64_t
     if (rc) return rc;
     GM_HIP(hipMemsetAsync(count, 0, 16, ctx->stream));
     hipLaunchKernelGGL(k_density_mask_count, dim3(grid_for((n + 63) >> 6, 256 * 16)), dim3(256), 0, ctx->stream,
-                       s.mask, n, count);
+                       a.sel.mask, n, count);
     GM_CHECK_LAUNCH();
     a.gate = count;
     a.gate_min = (unsigned long long)(DENS_PASS_SHARE * (fit - 1) * (double)n);
@@ -364,20 +360,19 @@ int density_check(const char* who, gm_ctx* ctx, int64_t n, const void* weight, c
   if (!ctx) return fail("NULL context");
   if (!g) return fail("NULL grid description");
   if (!grid || !tally) return fail("NULL grid or tally output");
-  if (n < 0 || (ids && n_ids < 0)) return fail("negative row count");
+  if (n < 0) return fail("negative row count");
   if (g->width < 1 || g->height < 1) return fail("width and height must be at least 1");
   if ((int64_t)g->width * g->height > 2147483647LL) return fail("width * height exceeds 2^31 - 1");
   if (!dens_bound_ok(g->xmin) || !dens_bound_ok(g->xmax) || !dens_bound_ok(g->ymin) || !dens_bound_ok(g->ymax))
     return fail("envelope bounds must be finite and within 2^31 in magnitude");
   if (!(g->xmax > g->xmin) || !(g->ymax > g->ymin)) return fail("flat or inverted envelope");
   if (g->xmax - g->xmin > 360.0 * 64) return fail("envelope wider than 64 turns");
-  if (mask && ids) return fail("mask and ids are exclusive");
+  if (const char* why = sel_check(mask, ids, n_ids)) return fail(why);
   if (g->path < 0 || g->path > 2) return fail("path must be 0, 1 or 2");
   if (g->path == 1 && dens_passes(g, weight != nullptr) > DENS_MAX_PASSES)
     return fail("path 1: the grid does not fit workgroup-private counters");
   if (g->workgroups < 0) return fail("negative workgroups");
-  if (!aligned_to<8>(weight) || !aligned_to<8>(mask) || !aligned_to<8>(ids) || !aligned_to<8>(grid) ||
-      !aligned_to<8>(tally))
+  if (!aligned_to<8>(weight) || !aligned_to<8>(grid) || !aligned_to<8>(tally))
     return fail("columns and outputs need 8-B alignment");
   return GM_OK;
 }
@@ -443,8 +438,8 @@ int gm_density_points(gm_ctx* ctx, const double* x, const double* y, const doubl
   }
   if (ids && n_ids == 0) return GM_OK;
   GM_HIP(hipSetDevice(ctx->device));
-  DensSrc s{x, y, weight, ArrowPts{nullptr, nullptr, 0, 0, 0}, nullptr, mask, ids};
-  return launch_density(ctx, SRC_COLS, false, s, n, ids ? n_ids : 0, g, grid, tally);
+  DensSrc s{x, y, weight, ArrowPts{nullptr, nullptr, 0, 0, 0}, nullptr};
+  return launch_density(ctx, SRC_COLS, false, s, row_sel(n, mask, ids, n_ids), g, grid, tally);
 }
 
 int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weight, int64_t n, const uint64_t* mask,
@@ -458,7 +453,7 @@ int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weig
   }
   if (ids && n_ids == 0) return GM_OK;
   GM_HIP(hipSetDevice(ctx->device));
-  DensSrc s{nullptr, nullptr, weight, ArrowPts{nullptr, nullptr, 0, 0, 0}, nullptr, mask, ids};
+  DensSrc s{nullptr, nullptr, weight, ArrowPts{nullptr, nullptr, 0, 0, 0}, nullptr};
   int src = SRC_POINT;
   bool f32 = false;
   if (n > 0) {
@@ -467,7 +462,7 @@ int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weig
     src = geom->type == GM_GEOM_POINT ? SRC_POINT : SRC_MULTI;
     f32 = geom->ordinal_bits == 32;
   }
-  return launch_density(ctx, src, f32, s, n, ids ? n_ids : 0, g, grid, tally);
+  return launch_density(ctx, src, f32, s, row_sel(n, mask, ids, n_ids), g, grid, tally);
 }
 
 int gm_density_sparse(gm_ctx* ctx, const double* grid, int32_t width, int32_t height, int64_t cap, int32_t* i,
@@ -480,25 +475,19 @@ int gm_density_sparse(gm_ctx* ctx, const double* grid, int32_t width, int32_t he
   GM_HIP(hipSetDevice(ctx->device));
   const int64_t cells = (int64_t)width * height, nb = (cells + SP_CELLS - 1) / SP_CELLS;
   DevTemps tmp(ctx->stream);
-  int32_t* counts;
-  int64_t *offsets, *partials;
-  int rc = tmp.alloc_async((size_t)nb * 4, &counts);
-  if (!rc) rc = tmp.alloc_async((size_t)(nb + 1) * 8, &offsets);
-  if (!rc) rc = tmp.alloc_async((size_t)scan_partials_len(nb) * 8, &partials);
+  CountScan cs;
+  int rc = cs.alloc(tmp, nb);
   if (rc) return rc;
   hipLaunchKernelGGL(k_density_sparse<false>, dim3((unsigned)nb), dim3(SCAN_TPB), 0, ctx->stream, grid, width, height,
-                     counts, (const int64_t*)nullptr, cap, i, j, w);
+                     cs.counts, (const int64_t*)nullptr, cap, i, j, w);
   GM_CHECK_LAUNCH();
-  launch_excl_scan(ctx->stream, counts, nb, offsets, partials, offsets + nb);
-  GM_CHECK_LAUNCH();
-  if (cap > 0) {
+  if ((rc = cs.scan(ctx))) return rc;
+  if (cap > 0) {   // the cells, before the count is waited for: one wait covers both
     hipLaunchKernelGGL(k_density_sparse<true>, dim3((unsigned)nb), dim3(SCAN_TPB), 0, ctx->stream, grid, width, height,
-                       counts, (const int64_t*)offsets, cap, i, j, w);
+                       cs.counts, (const int64_t*)cs.offsets, cap, i, j, w);
     GM_CHECK_LAUNCH();
   }
-  GM_HIP(hipMemcpyAsync(ctx->h_pinned, offsets + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
-  GM_HIP(hipStreamSynchronize(ctx->stream));
-  *n_cells = ctx->h_pinned[0];
+  if ((rc = cs.total(ctx, n_cells))) return rc;
   return *n_cells > cap ? GM_E_CAPACITY : GM_OK;
 }
 

@@ -6,9 +6,11 @@
 // Z3HBaseFilter; here a wave of 64 rows produces one 64-bit ballot word.
 //
 // Output pipeline (all on the context stream, deterministic, ids ascending):
-//   pass A  k_*_mask     : per-row predicate -> mask words + per-block match counts
+//   pass A  k_*_mask     : per-row predicate -> mask words + per-block match counts.  A kernel is its
+//                          predicate: the ballots, the mask words and the block count are pair_scan's
+//                          (columns: two rows per lane) or row_scan's (row keys, candidates) of gm_scan.hpp
 //   pass B  launch_excl_scan (gm_scan.hpp): exclusive scan of the per-block counts
-//   pass C  k_mask_to_ids: expand mask bits into row ids at the scanned offsets
+//   pass C  k_mask_to_ids: expand mask bits into row ids at the scanned offsets; read_i64: the match count
 // Pass C reads n/8 bytes of mask, so the ids cost ~1/80 of pass A's traffic plus 8 B per match.
 #include <string.h>
 
@@ -68,111 +70,6 @@ __device__ __forceinline__ bool bin_allowed(const int32_t* br, int nbr, int16_t 
   return false;
 }
 
-// block-level match count from per-wave popcounts
-__device__ __forceinline__ void block_count(int local, int32_t* block_counts) {
-  __shared__ int s_cnt;
-  if (threadIdx.x == 0) s_cnt = 0;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0 && local) atomicAdd(&s_cnt, local);
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt;
-}
-
-// pass A for Z3Filter: filter descriptor staged in LDS once per block
-__global__ __launch_bounds__(FTPB) void k_z3filter_mask(const int16_t* __restrict__ bin, const int64_t* __restrict__ z,
-                                                        int64_t n, const int32_t* __restrict__ fdesc, int fwords,
-                                                        const int32_t* __restrict__ bins, int nbr,
-                                                        uint64_t* __restrict__ mask, int32_t* __restrict__ block_counts) {
-  extern __shared__ int32_t s_f[];
-  for (int i = threadIdx.x; i < fwords; i += FTPB) s_f[i] = fdesc[i];
-  int32_t* s_bins = s_f + fwords;
-  for (int i = threadIdx.x; i < 2 * nbr; i += FTPB) s_bins[i] = bins[i];
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * FROWS;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int local = 0;
-#pragma unroll 4
-  for (int u = 0; u < FELEMS; ++u) {
-    const int64_t i = base + (int64_t)u * FTPB + threadIdx.x;
-    bool ok = false;
-    if (i < n) {
-      const int16_t b = bin[i];
-      const int64_t zz = z[i];
-      ok = bin_allowed(s_bins, nbr, b) && z3_in_bounds(s_f, b, zz);
-    }
-    const uint64_t w = __ballot(ok);
-    if (lane == 0) {
-      const int64_t word = (base + (int64_t)u * FTPB + wave * 64) >> 6;
-      if ((word << 6) < n) mask[word] = w;
-      local += __popcll(w);
-    }
-  }
-  block_count(local, block_counts);
-}
-
-// Z2Filter.inBounds (idx/filters/Z2Filter.scala:20-35)
-__global__ __launch_bounds__(FTPB) void k_z2filter_mask(const int64_t* __restrict__ z, int64_t n,
-                                                        const int32_t* __restrict__ xy, int nxy,
-                                                        uint64_t* __restrict__ mask, int32_t* __restrict__ block_counts) {
-  extern __shared__ int32_t s_xy[];
-  for (int i = threadIdx.x; i < 4 * nxy; i += FTPB) s_xy[i] = xy[i];
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * FROWS;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int local = 0;
-#pragma unroll 4
-  for (int u = 0; u < FELEMS; ++u) {
-    const int64_t i = base + (int64_t)u * FTPB + threadIdx.x;
-    bool ok = false;
-    if (i < n) {
-      const int64_t zz = z[i];
-      const int32_t x = z2_combine(zz), y = z2_combine(zz >> 1);
-      for (int k = 0; k < nxy; ++k) {
-        const int32_t* q = s_xy + 4 * k;
-        if (x >= q[0] && x <= q[2] && y >= q[1] && y <= q[3]) { ok = true; break; }
-      }
-    }
-    const uint64_t w = __ballot(ok);
-    if (lane == 0) {
-      const int64_t word = (base + (int64_t)u * FTPB + wave * 64) >> 6;
-      if ((word << 6) < n) mask[word] = w;
-      local += __popcll(w);
-    }
-  }
-  block_count(local, block_counts);
-}
-
-// strict: GeoTools BBOX on a point (inclusive) AND FastDuring (exclusive, ms)
-template <bool DURING>
-__global__ __launch_bounds__(FTPB) void k_strict_mask(const double* __restrict__ x, const double* __restrict__ y,
-                                                      const int64_t* __restrict__ t, int64_t n, double bx0, double by0,
-                                                      double bx1, double by1, int64_t lo, int64_t hi,
-                                                      uint64_t* __restrict__ mask, int32_t* __restrict__ block_counts) {
-  const int64_t base = (int64_t)blockIdx.x * FROWS;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int local = 0;
-#pragma unroll 4
-  for (int u = 0; u < FELEMS; ++u) {
-    const int64_t i = base + (int64_t)u * FTPB + threadIdx.x;
-    bool ok = false;
-    if (i < n) {
-      const double px = x[i], py = y[i];
-      ok = px >= bx0 && px <= bx1 && py >= by0 && py <= by1;
-      if (DURING) {
-        const int64_t tt = t[i];
-        ok = ok && tt > lo && tt < hi;
-      }
-    }
-    const uint64_t w = __ballot(ok);
-    if (lane == 0) {
-      const int64_t word = (base + (int64_t)u * FTPB + wave * 64) >> 6;
-      if ((word << 6) < n) mask[word] = w;
-      local += __popcll(w);
-    }
-  }
-  block_count(local, block_counts);
-}
-
 // Descriptor access.  Per-row reads of even wave-uniform descriptor words cost scalar loads plus
 // loop and exec-mask bookkeeping, and decoding x and y with Z3.combine costs ~60 VALU per row
 // (PMC: ~110 VALU per row, issue-bound at 45% of HBM).  The fast path (<= FBOX boxes,
@@ -205,9 +102,18 @@ __device__ __forceinline__ bool z3_row_fast(const uint64_t* bx, int nxy, const i
   return z3_in_bounds_time(fdesc, b, z);
 }
 
-// The generic path reads the descriptor straight from global memory with wave-uniform indices.
-template <bool FAST>
-__global__ __launch_bounds__(FTPB) void k_z3filter_mask_v(const sv2* __restrict__ bin2, const lv2* __restrict__ z2,
+// A pair of rows of a column of T, as its vector type V: one non-temporal load when the column is 16-B
+// aligned (4-B for the bins), else the two rows' own loads.
+template <bool VEC, class V, class T>
+__device__ __forceinline__ V load_pair(const T* __restrict__ col, int64_t p) {
+  if (VEC) return __builtin_nontemporal_load(&((const V*)col)[p]);
+  return V{col[2 * p], col[2 * p + 1]};
+}
+
+// pass A for Z3Filter.  The generic path reads the descriptor straight from global memory with
+// wave-uniform indices.
+template <bool FAST, bool VEC>
+__global__ __launch_bounds__(FTPB) void k_z3filter_mask_v(const int16_t* __restrict__ bin, const int64_t* __restrict__ z,
                                                           int64_t n, const uint64_t* __restrict__ dil,
                                                           const int32_t* __restrict__ fdesc,
                                                           const int32_t* __restrict__ bins, int nbr,
@@ -227,9 +133,9 @@ __global__ __launch_bounds__(FTPB) void k_z3filter_mask_v(const sv2* __restrict_
   };
   pair_scan(
       n, mask, block_counts,
-      [&](int64_t p, int u) { bv[u] = __builtin_nontemporal_load(&bin2[p]); zv[u] = __builtin_nontemporal_load(&z2[p]); },
+      [&](int64_t p, int u) { bv[u] = load_pair<VEC, sv2>(bin, p); zv[u] = load_pair<VEC, lv2>(z, p); },
       [&](int u, int j) { return j ? pred(bv[u].y, zv[u].y) : pred(bv[u].x, zv[u].x); },
-      [&](int64_t p) { return pred(((const int16_t*)bin2)[2 * p], ((const int64_t*)z2)[2 * p]); });
+      [&](int64_t p) { return pred(bin[2 * p], z[2 * p]); });
 }
 
 __device__ __forceinline__ bool z2_in_xy(const int32_t* __restrict__ xy, int nxy, int64_t zz) {
@@ -246,8 +152,9 @@ __device__ __forceinline__ bool z2_in_xy(const int32_t* __restrict__ xy, int nxy
 // sides: lo <= x  <=>  dilate(lo ^ 2^31) <= (z & X_BITS) ^ top.
 constexpr uint64_t Z2_XBITS = 0x5555555555555555ull;
 
-template <bool FAST>
-__global__ __launch_bounds__(FTPB) void k_z2filter_mask_v(const lv2* __restrict__ z2, int64_t n,
+// Z2Filter.inBounds (idx/filters/Z2Filter.scala:20-35)
+template <bool FAST, bool VEC>
+__global__ __launch_bounds__(FTPB) void k_z2filter_mask_v(const int64_t* __restrict__ z, int64_t n,
                                                           const uint64_t* __restrict__ dil,
                                                           const int32_t* __restrict__ xy, int nxy,
                                                           uint64_t* __restrict__ mask, int32_t* __restrict__ block_counts) {
@@ -267,14 +174,18 @@ __global__ __launch_bounds__(FTPB) void k_z2filter_mask_v(const lv2* __restrict_
     return pin;
   };
   pair_scan(
-      n, mask, block_counts, [&](int64_t p, int u) { zv[u] = __builtin_nontemporal_load(&z2[p]); },
+      n, mask, block_counts, [&](int64_t p, int u) { zv[u] = load_pair<VEC, lv2>(z, p); },
       [&](int u, int j) { return pred(j ? zv[u].y : zv[u].x); },
-      [&](int64_t p) { return pred(((const int64_t*)z2)[2 * p]); });
+      [&](int64_t p) { return pred(z[2 * p]); });
 }
 
-template <bool DURING>
-__global__ __launch_bounds__(FTPB) void k_strict_mask_v(const dv2* __restrict__ x, const dv2* __restrict__ y,
-                                                        const lv2* __restrict__ t, int64_t n, double bx0, double by0,
+// strict: GeoTools BBOX on a point (inclusive) AND FastDuring (exclusive, ms).  Without 16-B aligned columns
+// (VEC false) this scan keeps a lane per row: it streams 24 B a row and has no boxes to hold in registers,
+// and the pair layout's two 8-B loads per lane, 16 B apart, measured 3.80-3.91 ms per 1B rows against the
+// 3.34-3.60 of contiguous 8-B loads (profiles/scan_skeleton_ab.txt).
+template <bool DURING, bool VEC>
+__global__ __launch_bounds__(FTPB) void k_strict_mask_v(const double* __restrict__ x, const double* __restrict__ y,
+                                                        const int64_t* __restrict__ t, int64_t n, double bx0, double by0,
                                                         double bx1, double by1, int64_t lo, int64_t hi,
                                                         uint64_t* __restrict__ mask, int32_t* __restrict__ block_counts) {
   auto pred = [&](double px, double py, int64_t tt) {
@@ -282,20 +193,22 @@ __global__ __launch_bounds__(FTPB) void k_strict_mask_v(const dv2* __restrict__ 
     if (DURING) ok = ok && tt > lo && tt < hi;
     return ok;
   };
-  dv2 xv[FPAIRS], yv[FPAIRS];
-  lv2 tv[FPAIRS];
-  pair_scan(
-      n, mask, block_counts,
-      [&](int64_t p, int u) {
-        xv[u] = __builtin_nontemporal_load(&x[p]);
-        yv[u] = __builtin_nontemporal_load(&y[p]);
-        if (DURING) tv[u] = __builtin_nontemporal_load(&t[p]);
-        else tv[u] = lv2{0, 0};
-      },
-      [&](int u, int j) { return j ? pred(xv[u].y, yv[u].y, tv[u].y) : pred(xv[u].x, yv[u].x, tv[u].x); },
-      [&](int64_t p) {
-        return pred(((const double*)x)[2 * p], ((const double*)y)[2 * p], DURING ? ((const int64_t*)t)[2 * p] : 0);
-      });
+  if constexpr (!VEC) {
+    row_scan<4>(n, mask, block_counts, [&](int64_t i) { return pred(x[i], y[i], DURING ? t[i] : 0); });
+  } else {
+    dv2 xv[FPAIRS], yv[FPAIRS];
+    lv2 tv[FPAIRS];
+    pair_scan(
+        n, mask, block_counts,
+        [&](int64_t p, int u) {
+          xv[u] = load_pair<true, dv2>(x, p);
+          yv[u] = load_pair<true, dv2>(y, p);
+          if (DURING) tv[u] = load_pair<true, lv2>(t, p);
+          else tv[u] = lv2{0, 0};
+        },
+        [&](int u, int j) { return j ? pred(xv[u].y, yv[u].y, tv[u].y) : pred(xv[u].x, yv[u].x, tv[u].x); },
+        [&](int64_t p) { return pred(x[2 * p], y[2 * p], DURING ? t[2 * p] : 0); });
+  }
 }
 
 // pass C: one block per pass-A block; per (step, wave) popcount prefix gives each lane its slot
@@ -370,30 +283,16 @@ __global__ __launch_bounds__(FTPB) void k_filter_rows_mask(const uint8_t* __rest
   extern __shared__ int32_t s_f[];
   for (int i = threadIdx.x; i < fwords; i += FTPB) s_f[i] = fdesc[i];
   __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * FROWS;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int local = 0, nshort = 0;
-  for (int u = 0; u < FELEMS; ++u) {
-    const int64_t i = base + (int64_t)u * FTPB + threadIdx.x;
-    bool ok = false;
-    if (i < n) {
-      int16_t e;
-      int64_t zz;
-      if (row_key<Z3 ? 10 : 8>(rows, row_off, i, key_offset, e, zz)) {
-        ok = Z3 ? z3_in_bounds(s_f, e, zz) : z2_in_xy(s_f, fwords / 4, zz);   // Z3Filter.scala:26-28 / Z2Filter
-      } else {
-        ++nshort;
-      }
-    }
-    const uint64_t w = __ballot(ok);
-    if (lane == 0) {
-      const int64_t word = (base + (int64_t)u * FTPB + wave * 64) >> 6;
-      if ((word << 6) < n) mask[word] = w;
-      local += __popcll(w);
-    }
-  }
+  int nshort = 0;
+  row_scan(n, mask, block_counts, [&](int64_t i) {
+    int16_t e;
+    int64_t zz;
+    if (row_key<Z3 ? 10 : 8>(rows, row_off, i, key_offset, e, zz))
+      return Z3 ? z3_in_bounds(s_f, e, zz) : z2_in_xy(s_f, fwords / 4, zz);   // Z3Filter.scala:26-28 / Z2Filter
+    ++nshort;
+    return false;
+  });
   if (nshort && short_rows) atomicAdd(short_rows, (unsigned long long)nshort);
-  block_count(local, block_counts);
 }
 
 // ------------------------------------------------------------------ range scan of a sorted table
@@ -481,50 +380,28 @@ __global__ __launch_bounds__(FTPB) void k_range_mask(const uint16_t* __restrict_
                                                      int64_t nr, int64_t total, const int32_t* __restrict__ fdesc, int nxy,
                                                      FullFilter ff, uint64_t* __restrict__ mask,
                                                      int32_t* __restrict__ block_counts) {
-  const int64_t base = (int64_t)blockIdx.x * FROWS;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int local = 0;
-  for (int u = 0; u < FELEMS; ++u) {
-    const int64_t c = base + (int64_t)u * FTPB + threadIdx.x;
-    bool ok = false;
-    if (c < total) {
-      ok = true;
-      if (RF != RF_NONE || ENV || DUR) {
-        const int64_t row = cand_row(coff, start, nr, c);
-        if (RF == RF_Z3) ok = z3_in_bounds(fdesc, (int16_t)bin[row], (int64_t)z[row]);
-        if (RF == RF_Z2) {
-          const int64_t zz = (int64_t)z[row];
-          const int32_t x = z2_combine(zz), y = z2_combine(zz >> 1);
-          bool in = false;
-          for (int k = 0; k < nxy && !in; ++k) {
-            const int32_t* q = fdesc + 4 * k;
-            in = x >= q[0] && x <= q[2] && y >= q[1] && y <= q[3];
-          }
-          ok = in;
+  row_scan(total, mask, block_counts, [&](int64_t c) {
+    bool ok = true;
+    if (RF != RF_NONE || ENV || DUR) {
+      const int64_t row = cand_row(coff, start, nr, c);
+      if (RF == RF_Z3) ok = z3_in_bounds(fdesc, (int16_t)bin[row], (int64_t)z[row]);
+      if (RF == RF_Z2) ok = z2_in_xy(fdesc, nxy, (int64_t)z[row]);
+      if ((ENV || DUR) && ok) {
+        const int64_t r = ff.rows ? ff.rows[row] : row;
+        if (DUR) {
+          const int64_t t = ff.t[r];
+          ok = t > ff.t_lo && t < ff.t_hi;
         }
-        if ((ENV || DUR) && ok) {
-          const int64_t r = ff.rows ? ff.rows[row] : row;
-          if (DUR) {
-            const int64_t t = ff.t[r];
-            ok = t > ff.t_lo && t < ff.t_hi;
-          }
-          if (ENV && ok) {
-            const double x0 = ff.xmin[r], y0 = ff.ymin[r], x1 = ff.xmax[r], y1 = ff.ymax[r];
-            bool in = false;
-            for (int k = 0; k < ff.nbox && !in; ++k) in = env_intersects(x0, y0, x1, y1, ff.boxes + 4 * k);
-            ok = in;
-          }
+        if (ENV && ok) {
+          const double x0 = ff.xmin[r], y0 = ff.ymin[r], x1 = ff.xmax[r], y1 = ff.ymax[r];
+          bool in = false;
+          for (int k = 0; k < ff.nbox && !in; ++k) in = env_intersects(x0, y0, x1, y1, ff.boxes + 4 * k);
+          ok = in;
         }
       }
     }
-    const uint64_t w = __ballot(ok);
-    if (lane == 0) {
-      const int64_t word = (base + (int64_t)u * FTPB + wave * 64) >> 6;
-      if ((word << 6) < total) mask[word] = w;
-      local += __popcll(w);
-    }
-  }
-  block_count(local, block_counts);
+    return ok;
+  });
 }
 
 // compacted candidate indices -> table rows (-> input rows through perm)
@@ -658,6 +535,12 @@ int alloc_scan(gm_ctx* ctx, int64_t n, uint64_t* user_mask, size_t desc_words, S
   return GM_OK;
 }
 
+int CountScan::scan(gm_ctx* ctx) {
+  launch_excl_scan(ctx->stream, (const int32_t*)counts, nb, offsets, partials, offsets + nb);
+  GM_CHECK_LAUNCH();
+  return GM_OK;
+}
+
 // passes B and C + count readback
 int finish_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_cap, int64_t* n_match) {
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
@@ -670,12 +553,7 @@ int finish_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_c
                        ids_cap);
     GM_CHECK_LAUNCH();
   }
-  if (n_match) {
-    GM_HIP(hipMemcpyAsync(ctx->h_pinned, b.offsets + nblocks, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GM_HIP(hipStreamSynchronize(ctx->stream));
-    *n_match = ctx->h_pinned[0];
-  }
-  return GM_OK;
+  return n_match ? read_i64(ctx, b.offsets + nblocks, n_match) : GM_OK;
 }
 
 }  // namespace gm
@@ -719,16 +597,10 @@ int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len
   const uint64_t* d_dil = (const uint64_t*)b.desc;
   const int32_t* d_desc = b.desc + 2 * dil.size();
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
-  const size_t lds = desc.size() * 4;
-  if (aligned16(bin) && aligned16(z))
-    with_flags([&](auto FAST) {
-      hipLaunchKernelGGL(k_z3filter_mask_v<FAST()>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream,
-                         (const sv2*)bin, (const lv2*)z, n, d_dil, d_desc, d_desc + fwords, n_bin_ranges, b.mask,
-                         b.counts);
-    }, desc[0] <= FBOX && n_bin_ranges <= FBIN);
-  else
-    hipLaunchKernelGGL(k_z3filter_mask, dim3((unsigned)nblocks), dim3(FTPB), lds, ctx->stream, bin, z, n, d_desc,
-                       fwords, d_desc + fwords, n_bin_ranges, b.mask, b.counts);
+  with_flags([&](auto FAST, auto VEC) {
+    hipLaunchKernelGGL((k_z3filter_mask_v<FAST(), VEC()>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, bin, z,
+                       n, d_dil, d_desc, d_desc + fwords, n_bin_ranges, b.mask, b.counts);
+  }, desc[0] <= FBOX && n_bin_ranges <= FBIN, aligned16(bin) && aligned16(z));
   GM_CHECK_LAUNCH();
   return end_scan(ctx, n, b, ids, ids_cap, n_match);
 }
@@ -757,14 +629,10 @@ int gm_z2filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len
   const uint64_t* d_dil = (const uint64_t*)b.desc;
   const int32_t* d_xy = b.desc + 2 * dil.size();
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
-  if (aligned16(z))
-    with_flags([&](auto FAST) {
-      hipLaunchKernelGGL(k_z2filter_mask_v<FAST()>, dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const lv2*)z,
-                         n, d_dil, d_xy, nxy, b.mask, b.counts);
-    }, nxy <= FBOX);
-  else
-    hipLaunchKernelGGL(k_z2filter_mask, dim3((unsigned)nblocks), dim3(FTPB), xy.size() * 4 + 4, ctx->stream, z, n,
-                       d_xy, nxy, b.mask, b.counts);
+  with_flags([&](auto FAST, auto VEC) {
+    hipLaunchKernelGGL((k_z2filter_mask_v<FAST(), VEC()>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, z, n,
+                       d_dil, d_xy, nxy, b.mask, b.counts);
+  }, nxy <= FBOX, aligned16(z));
   GM_CHECK_LAUNCH();
   return end_scan(ctx, n, b, ids, ids_cap, n_match);
 }
@@ -791,13 +659,8 @@ static int filter_rows(gm_ctx* ctx, bool z3, const std::vector<int32_t>& desc, c
   }, z3);
   GM_CHECK_LAUNCH();
   // the short-row count is read back before the capacity is answered
-  return end_scan(ctx, n, b, ids, ids_cap, n_match, [&]() -> int {
-    if (!n_short) return GM_OK;
-    GM_HIP(hipMemcpyAsync(ctx->h_pinned, d_short, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GM_HIP(hipStreamSynchronize(ctx->stream));
-    *n_short = ctx->h_pinned[0];
-    return GM_OK;
-  });
+  return end_scan(ctx, n, b, ids, ids_cap, n_match,
+                  [&]() -> int { return n_short ? read_i64(ctx, d_short, n_short) : GM_OK; });
 }
 
 int gm_z3filter_scan_rows(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const uint8_t* rows,
@@ -835,17 +698,10 @@ int gm_strict_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t*
   if (rc) return rc;
   const int64_t nblocks = (n + FROWS - 1) / FROWS;
   const bool vec = aligned16(x) && aligned16(y) && (!has_during || aligned16(t_ms));
-  if (vec)
-    with_flags([&](auto D) {
-      hipLaunchKernelGGL((k_strict_mask_v<D()>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, (const dv2*)x,
-                         (const dv2*)y, (const lv2*)t_ms, n, bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask,
-                         b.counts);
-    }, has_during != 0);
-  else
-    with_flags([&](auto D) {
-      hipLaunchKernelGGL((k_strict_mask<D()>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, x, y, t_ms, n,
-                         bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask, b.counts);
-    }, has_during != 0);
+  with_flags([&](auto D, auto VEC) {
+    hipLaunchKernelGGL((k_strict_mask_v<D(), VEC()>), dim3((unsigned)nblocks), dim3(FTPB), 0, ctx->stream, x, y, t_ms,
+                       n, bbox[0], bbox[1], bbox[2], bbox[3], lo, hi, b.mask, b.counts);
+  }, has_during != 0, vec);
   GM_CHECK_LAUNCH();
   return end_scan(ctx, n, b, ids, ids_cap, n_match);
 }
@@ -933,9 +789,8 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
                      (const uint16_t*)bin, (const uint64_t*)z, n, d_rg, nr, start, coff);
   hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, s, coff, nr);
   GM_CHECK_LAUNCH();
-  GM_HIP(hipMemcpyAsync(ctx->h_pinned, coff + nr, 8, hipMemcpyDeviceToHost, s));
-  GM_HIP(hipStreamSynchronize(s));  // dr is pageable; the candidate count sizes the pass below
-  const int64_t total = ctx->h_pinned[0];
+  int64_t total = 0;   // the candidate count sizes the pass below (and dr is pageable: the wait covers its copy)
+  if ((rc = read_i64(ctx, coff + nr, &total))) return rc;
   if (n_scanned) *n_scanned = total;
   int64_t nm = 0, ne = 0;
   if (total > 0) {

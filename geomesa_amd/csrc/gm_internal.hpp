@@ -132,6 +132,14 @@ class DevTemps {
   std::vector<Buf> bufs_;
 };
 
+// one int64 of device memory (a scan's total, a counter) through h_pinned[0]; synchronises the stream
+inline int read_i64(gm_ctx* ctx, const void* dev, int64_t* host) {
+  GM_HIP(hipMemcpyAsync(ctx->h_pinned, dev, 8, hipMemcpyDeviceToHost, ctx->stream));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  *host = ctx->h_pinned[0];
+  return GM_OK;
+}
+
 bool host_pinned(const void* p);
 bool device_memory(const void* p);   // device (hipMalloc) memory, as opposed to host memory
 int ctx_copy_stream(gm_ctx* ctx);   // creates copy_stream and its events on first use

@@ -616,10 +616,10 @@ static int join_staged(gm_ctx* ctx, const double* px, const double* py, ArrowPts
 static int join_result(gm_ctx* ctx, const char* what, unsigned long long* counter, bool write, int64_t cap,
                        int64_t* n_pairs) {
   if (!n_pairs) return GM_OK;
-  GM_HIP(hipMemcpyAsync(ctx->h_pinned, counter, 8, hipMemcpyDeviceToHost, ctx->stream));
-  const int rc = take_fault(ctx, what);   // synchronises
+  int64_t total = 0;
+  int rc = read_i64(ctx, counter, &total);
+  if (!rc) rc = take_fault(ctx, what);
   if (rc) return rc;
-  const int64_t total = ctx->h_pinned[0];
   *n_pairs = total;
   return (write && total > cap) ? GM_E_CAPACITY : GM_OK;
 }

@@ -1,5 +1,8 @@
-// gm_scan.hpp -- shared pieces of the mask -> block scan -> ordered compaction pipeline
-// (gm_filter.hip; the fused query scan in gm_pip.hip).
+// gm_scan.hpp -- what the streaming scans share: the two mask-pass skeletons (pair_scan: two rows per
+// lane; row_scan: one), the device-wide exclusive scan with its count -> scan -> total helper
+// (CountScan), the row selection of the aggregating scans (RowSel, sel_row) and the mask -> block scan ->
+// ordered compaction pipeline of the filter scans (alloc_scan / finish_scan / end_scan).  Used by
+// gm_filter.hip, gm_geom_filter.hip, gm_pip_query.hip, gm_density.hip and gm_bin.hip.
 #pragma once
 
 #include "gm_internal.hpp"
@@ -8,21 +11,22 @@ namespace gm {
 
 constexpr int FTPB = 256;             // threads per block
 #ifndef GM_FELEMS
-#define GM_FELEMS 16  // sweep (tools/filter_ab.sh, z3filter_scan ms per 1B rows): 4 2.27, 8 1.81-1.94, 16 1.68-1.80, 32 1.92-1.94
+#define GM_FELEMS 16  // sweep (profiles/r2_felems_sweep.txt, z3filter_scan ms per 1B rows): 4 2.27, 8 1.81-1.94, 16 1.68-1.80, 32 1.92-1.94
 #endif
 constexpr int FELEMS = GM_FELEMS;     // rows per thread per block
 static_assert(FELEMS % 2 == 0 && FELEMS >= 2, "pair layout");
 constexpr int FROWS = FTPB * FELEMS;  // rows per block (4096) -> 64 mask words
 
-// ------------------------------------------------------------------ vectorised pass A
-// The scalar kernels of gm_filter.hip move 2 B (bin) and 8 B (z) per lane per load instruction; on gfx950 narrow
-// per-lane accesses stream at roughly half the 16-B rate.  The _v variants use the layout of the
-// encode kernels: each lane takes PAIRS of consecutive rows, one 16-B load per 8-byte column
-// (z, x, y, t) and one 4-B load of the two bins, and pair p of lane l in step u sits at
-// block_base + u*256 + l, so every wave instruction reads one contiguous 1 KiB run.  A wave step
-// covers 128 rows: ballot(row 2l) and ballot(row 2l+1) interleave bit by bit into the two 64-bit
-// mask words of those rows.  A block still covers FROWS = 4096 rows (8 steps), so block_counts,
-// the count scan and k_mask_to_ids are shared with the scalar kernels.
+// ------------------------------------------------------------------ pass A, the pair layout
+// A lane-per-row load moves 2 B (bin) and 8 B (z) per lane per instruction; on gfx950 narrow per-lane
+// accesses stream at roughly half the 16-B rate.  The column scans (k_*_mask_v, k_query_mask) use the
+// layout of the encode kernels: each lane takes PAIRS of consecutive rows, one 16-B load per 8-byte
+// column (z, x, y, t) and one 4-B load of the two bins (VEC; two scalar loads per column when a column
+// is not 16-B aligned), and pair p of lane l in step u sits at block_base + u*256 + l, so every wave
+// instruction reads one contiguous 1 KiB run.  A wave step covers 128 rows: ballot(row 2l) and
+// ballot(row 2l+1) interleave bit by bit into the two 64-bit mask words of those rows.  A block covers
+// FROWS = 4096 rows (8 steps), as a row_scan block does, so block_counts, the count scan and
+// k_mask_to_ids are shared with the lane-per-row kernels.
 typedef short sv2 __attribute__((ext_vector_type(2)));
 constexpr int FPAIRS = FELEMS / 2;   // pair steps per lane
 
@@ -79,6 +83,31 @@ __device__ __forceinline__ void pair_scan(int64_t n, uint64_t* __restrict__ mask
     put_pair_words(be, bo, mask, ((pbase + (int64_t)u * FTPB + wave * 64) * 2) >> 6, nwords);
   }
   block_count_waves(cnt, block_counts);
+}
+
+// The lane-per-row counterpart (row keys, candidate spaces: the row's bytes are found per row): PRED(i)
+// evaluates row i < total; step u of a block takes rows block_base + u*256 + [0, 256), one ballot word
+// per wave.  UNROLL steps are in flight at once: 1 for a predicate that searches or walks a descriptor, 4 for
+// one that only streams its columns.
+template <int UNROLL = 1, class Pred>
+__device__ __forceinline__ void row_scan(int64_t total, uint64_t* __restrict__ mask, int32_t* __restrict__ block_counts,
+                                         Pred pred) {
+  const int64_t base = (int64_t)blockIdx.x * FROWS;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int cnt = 0;
+#pragma unroll UNROLL
+  for (int u = 0; u < FELEMS; ++u) {
+    const int64_t i = base + (int64_t)u * FTPB + threadIdx.x;
+    bool ok = false;
+    if (i < total) ok = pred(i);
+    const uint64_t w = __ballot(ok);
+    if (lane == 0) {
+      const int64_t word = (base + (int64_t)u * FTPB + wave * 64) >> 6;
+      if ((word << 6) < total) mask[word] = w;
+      cnt += __popcll(w);
+    }
+  }
+  block_count_waves(cnt, block_counts);   // reads lane 0's
 }
 
 // Device-wide exclusive scan, two levels (block counts of the mask scans, radix-sort histograms).
@@ -179,6 +208,25 @@ inline void launch_excl_scan(hipStream_t s, const TIn* in, int64_t n, TOut* out,
     hipLaunchKernelGGL((k_scan_apply<TIn, TOut>), dim3((unsigned)nchunks), dim3(SCAN_TPB), 0, s, in, n, partials, out);
 }
 
+// One call's count -> scan -> total over nb blocks, in the stream's pool: the caller's count kernel fills
+// counts[nb], scan() enqueues the exclusive scan into offsets[nb] (the total behind them), total() reads
+// the total back (synchronises); a write kernel then takes block b's output from offsets[b] on.
+struct CountScan {
+  int64_t nb = 0;
+  int32_t* counts = nullptr;
+  int64_t* offsets = nullptr;
+  int64_t* partials = nullptr;
+  int alloc(DevTemps& tmp, int64_t nblocks) {
+    nb = nblocks;
+    int rc = tmp.alloc_async((size_t)nb * 4, &counts);
+    if (!rc) rc = tmp.alloc_async((size_t)(nb + 1) * 8, &offsets);
+    if (!rc) rc = tmp.alloc_async((size_t)scan_partials_len(nb) * 8, &partials);
+    return rc;
+  }
+  int scan(gm_ctx* ctx);   // gm_filter.hip, with finish_scan: one instantiation of the scan kernels
+  int total(gm_ctx* ctx, int64_t* t) { return read_i64(ctx, offsets + nb, t); }
+};
+
 struct ScanBufs {
   uint64_t* mask = nullptr;
   int32_t* counts = nullptr;
@@ -206,16 +254,64 @@ inline int end_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t i
   return end_scan(ctx, n, b, ids, ids_cap, n_match, [] { return (int)GM_OK; });
 }
 
+// ------------------------------------------------------------------ row selection of an aggregating scan
+// Every row, the rows of a mask, or the rows ids names (gm_density_*, gm_bin_*: what a scan or a table
+// query kept).
+enum : int { SEL_NONE = 0, SEL_MASK = 1, SEL_IDS = 2 };
+struct RowSel {
+  int64_t n;              // rows (or slots) of the source
+  int64_t units;          // entries of the selection: n, or the entries of ids
+  const uint64_t* mask;   // bit r & 63 of word r >> 6 selects row r
+  const int64_t* ids;     // the selected rows, in the caller's order
+};
+inline RowSel row_sel(int64_t n, const uint64_t* mask, const int64_t* ids, int64_t n_ids) {
+  return RowSel{n, ids ? n_ids : n, mask, ids};
+}
+inline int sel_of(const RowSel& s) { return s.ids ? SEL_IDS : (s.mask ? SEL_MASK : SEL_NONE); }
+// the selection errors of an entry point that do not depend on its source; null: none
+inline const char* sel_check(const uint64_t* mask, const int64_t* ids, int64_t n_ids) {
+  if (ids && n_ids < 0) return "negative id count";
+  if (mask && ids) return "mask and ids are exclusive";
+  if (!aligned_to<8>(mask) || !aligned_to<8>(ids)) return "columns and outputs need 8-B alignment";
+  return nullptr;
+}
+
+__device__ __forceinline__ bool mask_bit(const uint64_t* __restrict__ mask, int64_t r) {
+  return (mask[r >> 6] >> (r & 63)) & 1ull;
+}
+// the bits of rows 2p and 2p + 1 out of their word w = mask[p >> 5]
+__device__ __forceinline__ void mask_pair(uint64_t w, int64_t p, bool& even, bool& odd) {
+  const uint64_t b = w >> ((2 * p) & 63);
+  even = b & 1ull;
+  odd = (b >> 1) & 1ull;
+}
+// entry u < s.units of the selection -> row r.  1: selected; 0: not; -1: an id outside [0, n), for the
+// caller's tally (the count comes back as a value: a counter taken by reference cost k_density's ids
+// instantiations 4 SGPRs and one of them a wave of occupancy)
+template <int SEL>
+__device__ __forceinline__ int sel_row(const RowSel& s, int64_t u, int64_t& r) {
+  if (SEL == SEL_IDS) {
+    r = s.ids[u];
+    return (uint64_t)r < (uint64_t)s.n ? 1 : -1;
+  }
+  r = u;
+  return SEL != SEL_MASK || mask_bit(s.mask, u);
+}
+
 // ------------------------------------------------------------------ candidate space of a table scan
-// candidate c -> its range (upper_bound over the scanned offsets, minus one) -> table row
-__device__ __forceinline__ int64_t cand_row(const int64_t* __restrict__ coff, const int64_t* __restrict__ start,
-                                            int64_t nr, int64_t c) {
-  int64_t lo = 0, hi = nr;
+// the entry of the scanned offsets off[0, n) that holds c: upper_bound, minus one
+__device__ __forceinline__ int64_t offset_slot(const int64_t* __restrict__ off, int64_t n, int64_t c) {
+  int64_t lo = 0, hi = n;
   while (lo < hi) {
     const int64_t m = (lo + hi) >> 1;
-    if (coff[m] <= c) lo = m + 1; else hi = m;
+    if (off[m] <= c) lo = m + 1; else hi = m;
   }
-  const int64_t r = lo - 1;
+  return lo - 1;
+}
+// candidate c -> its range -> table row
+__device__ __forceinline__ int64_t cand_row(const int64_t* __restrict__ coff, const int64_t* __restrict__ start,
+                                            int64_t nr, int64_t c) {
+  const int64_t r = offset_slot(coff, nr, c);
   return start[r] + (c - coff[r]);
 }
 

@@ -129,21 +129,60 @@ def _torch():
     return torch
 
 
-def _dev_col(a, dtype):
-    """Return a contiguous GPU tensor of `dtype` for column `a` (no copy if already one)."""
+def _dev_col(a, dtype, dev=None):
+    """A contiguous tensor of `dtype` on `dev` (default: the context's GPU) for column `a` (no copy if
+    already one); None passes through."""
     torch = _torch()
-    ctx = _lib.context()
-    dev = torch.device("cuda", ctx.device)
-    if isinstance(a, torch.Tensor):
-        t = a
-        if t.device != dev:
-            t = t.to(dev)
-        if t.dtype != dtype:
-            t = t.to(dtype)
-        return t.contiguous()
-    arr = np.ascontiguousarray(np.asarray(a), dtype={torch.float64: np.float64, torch.int64: np.int64,
-                                                     torch.int16: np.int16}[dtype])
-    return torch.from_numpy(arr).to(dev)
+    if a is None:
+        return None
+    if dev is None:
+        dev = torch.device("cuda", _lib.context().device)
+    if not isinstance(a, torch.Tensor):
+        a = np.ascontiguousarray(np.asarray(a), dtype={torch.float64: np.float64, torch.int64: np.int64,
+                                                       torch.int32: np.int32, torch.int16: np.int16,
+                                                       torch.uint8: np.uint8}[dtype])
+        a = torch.from_numpy(a if a.flags.writeable else a.copy())   # torch wants a writable array
+    if a.device != dev:
+        a = a.to(dev)
+    if a.dtype != dtype:
+        a = a.to(dtype)
+    return a.contiguous()
+
+
+def _pack_mask(mask, n, dev):
+    """A selection as the kernels' mask words: int64 words pass through, a bool tensor / array of n rows
+    is packed (bit r % 64 of word r // 64)."""
+    torch = _torch()
+    if not isinstance(mask, torch.Tensor):
+        mask = torch.from_numpy(np.ascontiguousarray(mask))
+    mask = mask.to(dev)
+    words = (n + 63) // 64
+    if mask.dtype == torch.bool:
+        if mask.numel() != n:
+            raise ValueError("a boolean mask needs one entry per row (%d), got %d" % (n, mask.numel()))
+        m = torch.zeros(words * 64, dtype=torch.int64, device=dev)
+        m[:n] = mask.to(torch.int64)
+        return (m.view(-1, 64) << torch.arange(64, device=dev, dtype=torch.int64)).sum(1).contiguous()
+    if mask.dtype != torch.int64 or mask.numel() < words:
+        raise ValueError("a mask is a bool tensor of n rows or int64 words (ceil(n / 64) of them)")
+    return mask.contiguous()
+
+
+def _selection(n, mask, ids, dev):
+    """The rows of n an aggregating scan (density, BIN) takes -- every row, the rows of a mask or the rows
+    ids names -- as the entry points want them: (mask words or None, ids or None, n_ids)."""
+    torch = _torch()
+    if mask is not None and ids is not None:
+        raise ValueError("give a mask or ids, not both")
+    if mask is not None:
+        mask = _pack_mask(mask, n, dev)
+    n_ids = 0
+    if ids is not None:
+        ids = _dev_col(ids, torch.int64, dev)
+        n_ids = ids.numel()
+        if n_ids == 0:   # an empty selection still is one: a valid pointer for it
+            ids = torch.zeros(1, dtype=torch.int64, device=dev)
+    return mask, ids, n_ids
 
 
 def _summary():

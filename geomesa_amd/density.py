@@ -71,25 +71,6 @@ class GridSnap:
         return self.x(self.i(x)), self.y(self.j(y))
 
 
-def _pack_mask(mask, n, dev):
-    """A selection as the kernel's mask words: int64 words pass through, a bool tensor / array of n rows
-    is packed (bit r % 64 of word r // 64)."""
-    import torch
-    if not isinstance(mask, torch.Tensor):
-        mask = torch.from_numpy(np.ascontiguousarray(mask))
-    mask = mask.to(dev)
-    words = (n + 63) // 64
-    if mask.dtype == torch.bool:
-        if mask.numel() != n:
-            raise ValueError("a boolean mask needs one entry per row (%d), got %d" % (n, mask.numel()))
-        m = torch.zeros(words * 64, dtype=torch.int64, device=dev)
-        m[:n] = mask.to(torch.int64)
-        return (m.view(-1, 64) << torch.arange(64, device=dev, dtype=torch.int64)).sum(1).contiguous()
-    if mask.dtype != torch.int64 or mask.numel() < words:
-        raise ValueError("a mask is a bool tensor of n rows or int64 words (ceil(n / 64) of them)")
-    return mask.contiguous()
-
-
 class RenderingGrid:
     """RenderingGrid(env, xSize, ySize) for point features (RenderingGrid.scala:25-64), the pixels a dense
     float64 [height, width] device tensor; env = (xmin, ymin, xmax, ymax).
@@ -125,33 +106,17 @@ class RenderingGrid:
         return _lib.DensityGrid(self.env[0], self.env[1], self.env[2], self.env[3], self.width, self.height,
                                 self.workgroups, self.path)
 
-    def _selection(self, n, mask, ids):
-        import torch
-        from .curve import _dev_col
-        if mask is not None and ids is not None:
-            raise ValueError("give a mask or ids, not both")
-        dev = self.grid.device
-        if mask is not None:
-            mask = _pack_mask(mask, n, dev)
-        n_ids = 0
-        if ids is not None:
-            ids = _dev_col(ids, torch.int64)
-            n_ids = ids.numel()
-            if n_ids == 0:   # an empty selection still is one: a valid pointer for it
-                ids = torch.zeros(1, dtype=torch.int64, device=dev)
-        return mask, ids, n_ids
-
     def render(self, x, y, weight=None, mask=None, ids=None):
         """RenderingGrid.render(Point, weight) for rows of x / y columns (weight: None = 1.0, or a column)."""
         import torch
-        from .curve import _dev_col
+        from .curve import _dev_col, _selection
         x = _dev_col(x, torch.float64)
         y = _dev_col(y, torch.float64)
         w = _dev_col(weight, torch.float64) if weight is not None else None
         n = x.numel()
         if y.numel() != n or (w is not None and w.numel() != n):
             raise ValueError("x, y and weight must have one entry per row")
-        mask, ids, n_ids = self._selection(n, mask, ids)
+        mask, ids, n_ids = _selection(n, mask, ids, self.grid.device)
         ctx = _lib.context(self._device)
         g = self._c()
         check(ctx.lib.gm_density_points(ctx.handle, ptr(x), ptr(y), ptr(w), n, ptr(mask), ptr(ids), n_ids,
@@ -163,7 +128,7 @@ class RenderingGrid:
         `kind`); every point of a MultiPoint gets the slot's weight (RenderingGrid.scala:57-64)."""
         import torch
         from .arrow import _as_geom
-        from .curve import _dev_col
+        from .curve import _dev_col, _selection
         col = _as_geom(col, kind, flip_axis)
         if col.kind not in ("point", "multipoint"):
             raise ValueError("the density scan renders Point and MultiPoint columns")
@@ -171,7 +136,7 @@ class RenderingGrid:
         w = _dev_col(weight, torch.float64) if weight is not None else None
         if w is not None and w.numel() != n:
             raise ValueError("weight must have one entry per slot")
-        mask, ids, n_ids = self._selection(n, mask, ids)
+        mask, ids, n_ids = _selection(n, mask, ids, self.grid.device)
         ctx = _lib.context(self._device)
         g = self._c()
         cs = col.c_struct()

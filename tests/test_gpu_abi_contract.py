@@ -40,12 +40,12 @@ others as in "all"):
   gm_xz3_index      the six envelope columns and out at 16 B, status at 2 B
       all                 k_xz3_index_v; each of the eight +1   k_xz3_index
   gm_z3filter_scan  bin, z at 16 B (mask, ids: any 8-B address)
-      all                 k_z3filter_mask_v<true>;   bin+1, z+1   k_z3filter_mask
-      mask+1, ids+1       k_z3filter_mask_v<true> and k_mask_to_ids on 8-B aligned outputs
+      all                 k_z3filter_mask_v<FAST = true, VEC = true>;   bin+1, z+1   k_z3filter_mask_v<true, false>
+      mask+1, ids+1       k_z3filter_mask_v<true, true> and k_mask_to_ids on 8-B aligned outputs
   gm_z2filter_scan  z at 16 B
-      all                 k_z2filter_mask_v<true>;   z+1   k_z2filter_mask;   mask+1, ids+1 as above
+      all                 k_z2filter_mask_v<true, true>;   z+1   k_z2filter_mask_v<true, false>;   mask+1, ids+1 as above
   gm_strict_scan    x, y, t_ms (with a during) at 16 B
-      all                 k_strict_mask_v<true>;     x+1, y+1, t_ms+1   k_strict_mask<true>;   mask+1, ids+1
+      all                 k_strict_mask_v<DURING = true, VEC = true>;   x+1, y+1, t_ms+1   k_strict_mask_v<true, false>;   mask+1, ids+1
   gm_query_scan     x, y, t_ms (with a during) at 16 B, with a geometry term
       all                 k_query_mask<VEC = true, true, ..>;  x+1, y+1, t_ms+1   k_query_mask<false, true, ..>;  mask+1, ids+1
   gm_z3_histogram   x, y, t_ms at 16 B (LDS-counter path)

@@ -13,7 +13,8 @@ Inputs make a wrong instantiation visible, and the `distinct` assertions prove i
             such batch also holds a time before 1970, which fails in both modes
   status    the returned array equals the oracle's (a kernel without STATUS leaves the 0xA5 fill); without a
             status the failed rows make the call answer GM_E_ELEMENT
-  aligned   "moved" shifts one column by 8 B: same expectation, the scalar kernel
+  aligned   "moved" shifts one column by 8 B: same expectation, the kernel without 16-B loads (scalar index
+            kernels; the scans' VEC = false instantiations)
   during / op / boxes   the scans' masks differ between neighbouring grid points
 The Arrow Z3 key with dtg = NULL indexes every row at time 0, which normalises to the same z in every
 period: there the period shows only through the variants that have a dtg column.
@@ -325,7 +326,7 @@ def strict_masks():
 
 
 def test_strict_scan_grid(gpu):
-    """during x aligned / x moved: k_strict_mask_v<D> and k_strict_mask<D>."""
+    """during x aligned / x moved: k_strict_mask_v<D, VEC>, all four."""
     x, y, t = scan_cols()[:3]
     masks = strict_masks()
     for d, moved in itertools.product((0, 1), (0, MOVE)):
@@ -341,9 +342,14 @@ def _strips(k, bits):
     return [[2 * j * w, 0, (2 * j + 1) * w - 1, (1 << bits) - 1] for j in range(k)]
 
 
+# five bin ranges (more than FBIN = 4), every other five weeks of 2020's weekly bins 2608..2661
+BIN_RANGES = np.array([[2608 + 12 * j, 2612 + 12 * j] for j in range(5)], np.int16)
+
+
 @functools.lru_cache(maxsize=None)
 def filter_masks(entry):
-    """({boxes: filter bytes}, {boxes: mask}) for 2 and 5 boxes."""
+    """({boxes: filter bytes}, {(boxes, bin ranges): mask}) for 2 and 5 boxes and, for Z3, 2 boxes with the
+    five BIN_RANGES."""
     import oracle as O
     from geomesa_amd import filters as F
     x, y, t, b, z, z2 = scan_cols()
@@ -352,29 +358,32 @@ def filter_masks(entry):
     for k in (2, 5):
         fbs[k] = (F.serialize_to_bytes(F.Z3Filter(_strips(k, 21), [], 32767, -32768)) if z3 else
                   F.z2_serialize_to_bytes(F.Z2Filter(_strips(k, 31))))
-        masks[k] = O.z3filter_scan(fbs[k], [], b, z) if z3 else O.z2filter_scan(fbs[k], z2)
-    all_differ(masks, entry + " boxes")
+        masks[(k, 0)] = O.z3filter_scan(fbs[k], [], b, z) if z3 else O.z2filter_scan(fbs[k], z2)
+    if z3:
+        masks[(2, 5)] = O.z3filter_scan(fbs[2], BIN_RANGES, b, z)
+    all_differ(masks, entry + " boxes and bin ranges")
     return fbs, masks
 
 
 @pytest.mark.parametrize("entry", ["gm_z3filter_scan", "gm_z2filter_scan"])
 def test_filter_scan_grid(gpu, entry):
-    """{at most FBOX = 4 boxes, more than 4} on aligned columns (k_*filter_mask_v<true> / <false>) and the
-    scalar kernel on a moved z."""
+    """{at most FBOX = 4 boxes, more than 4} x {aligned, z moved}: k_*filter_mask_v<FAST, VEC>, all four; and
+    for Z3 more than FBIN = 4 bin ranges on the moved z, the other way to <false, false>."""
     x, y, t, b, z, z2 = scan_cols()
     z3 = entry == "gm_z3filter_scan"
     fbs, masks = filter_masks(entry)
-    for k, moved in ((2, 0), (5, 0), (5, MOVE)):
+    for k, nbr, moved in ((2, 0, 0), (5, 0, 0), (2, 0, MOVE), (5, 0, MOVE)) + (((2, 5, MOVE),) if z3 else ()):
         fb = np.frombuffer(fbs[k], U8).copy()
         if z3:
             ins = [Guarded.of(b), Guarded.of(z, moved)]
-            call = lambda m, i, c, nm: gpu.lib.gm_z3filter_scan(gpu.handle, fb.ctypes.data, len(fb), None, 0,  # noqa: E731
+            br = BIN_RANGES.ctypes.data if nbr else None
+            call = lambda m, i, c, nm: gpu.lib.gm_z3filter_scan(gpu.handle, fb.ctypes.data, len(fb), br, nbr,  # noqa: E731
                                                                 P(ins[0]), P(ins[1]), SCAN_N, m, i, c, nm)
         else:
             ins = [Guarded.of(z2, moved)]
             call = lambda m, i, c, nm: gpu.lib.gm_z2filter_scan(gpu.handle, fb.ctypes.data, len(fb), P(ins[0]),  # noqa: E731
                                                                 SCAN_N, m, i, c, nm)
-        run_scan(gpu, ins, call, masks[k], (entry, k, moved))
+        run_scan(gpu, ins, call, masks[(k, nbr)], (entry, k, nbr, moved))
 
 
 @pytest.mark.parametrize("entry", ["gm_z3filter_scan_rows", "gm_z2filter_scan_rows"])
