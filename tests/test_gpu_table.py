@@ -64,19 +64,21 @@ def test_sort_keys_parity(gpu, n, kind, sharded, mode):
     shard = rng.integers(0, 4, n).astype(np.uint8) if sharded else None
     ctx = _lib.context()
     ctx.set_param(_lib.GM_PARAM_SORT_MODE, mode)
-    db, dz = torch.from_numpy(bins).cuda(), torch.from_numpy(z).cuda()
-    ds = torch.from_numpy(shard).cuda() if sharded else None
-    ob, oz, op = torch.empty_like(db), torch.empty_like(dz), torch.empty(n, dtype=torch.int64, device="cuda")
-    os_ = torch.empty_like(ds) if sharded else None
-    _lib.check(ctx.lib.gm_sort_keys(ctx.handle, _lib.ptr(ds), _lib.ptr(db), _lib.ptr(dz), n, _lib.ptr(os_),
-                                    _lib.ptr(ob), _lib.ptr(oz), _lib.ptr(op)), "sort")
+    try:
+        db, dz = torch.from_numpy(bins).cuda(), torch.from_numpy(z).cuda()
+        ds = torch.from_numpy(shard).cuda() if sharded else None
+        ob, oz, op = torch.empty_like(db), torch.empty_like(dz), torch.empty(n, dtype=torch.int64, device="cuda")
+        os_ = torch.empty_like(ds) if sharded else None
+        _lib.check(ctx.lib.gm_sort_keys(ctx.handle, _lib.ptr(ds), _lib.ptr(db), _lib.ptr(dz), n, _lib.ptr(os_),
+                                        _lib.ptr(ob), _lib.ptr(oz), _lib.ptr(op)), "sort")
+        last = ctx.get_param(_lib.GM_PARAM_SORT_LAST)
+    finally:
+        ctx.set_param(_lib.GM_PARAM_SORT_MODE, 0)
     order = expected_order(bins, z, shard)
     assert np.array_equal(as_np(op), order)
     assert np.array_equal(as_np(ob), bins[order]) and np.array_equal(as_np(oz), z[order])
     if sharded:
         assert np.array_equal(as_np(os_), shard[order])
-    last = ctx.get_param(_lib.GM_PARAM_SORT_LAST)
-    ctx.set_param(_lib.GM_PARAM_SORT_MODE, 0)
     if mode == 1:
         assert last < 256
     elif kind in ("rand", "keys", "narrow", "runs") and n > 100_000:
@@ -190,12 +192,14 @@ def test_sort_keys_sample_misses_a_varying_bit(gpu, where, mode):
         z[odd] |= 1 << 62
     ctx = _lib.context()
     ctx.set_param(_lib.GM_PARAM_SORT_MODE, mode)
-    db, dz, ds = torch.from_numpy(bins).cuda(), torch.from_numpy(z).cuda(), torch.from_numpy(shard).cuda()
-    ob, oz, os_ = torch.empty_like(db), torch.empty_like(dz), torch.empty_like(ds)
-    op = torch.empty(n, dtype=torch.int64, device="cuda")
-    _lib.check(ctx.lib.gm_sort_keys(ctx.handle, _lib.ptr(ds), _lib.ptr(db), _lib.ptr(dz), n, _lib.ptr(os_),
-                                    _lib.ptr(ob), _lib.ptr(oz), _lib.ptr(op)), "sort")
-    ctx.set_param(_lib.GM_PARAM_SORT_MODE, 0)
+    try:
+        db, dz, ds = torch.from_numpy(bins).cuda(), torch.from_numpy(z).cuda(), torch.from_numpy(shard).cuda()
+        ob, oz, os_ = torch.empty_like(db), torch.empty_like(dz), torch.empty_like(ds)
+        op = torch.empty(n, dtype=torch.int64, device="cuda")
+        _lib.check(ctx.lib.gm_sort_keys(ctx.handle, _lib.ptr(ds), _lib.ptr(db), _lib.ptr(dz), n, _lib.ptr(os_),
+                                        _lib.ptr(ob), _lib.ptr(oz), _lib.ptr(op)), "sort")
+    finally:
+        ctx.set_param(_lib.GM_PARAM_SORT_MODE, 0)
     order = expected_order(bins, z, shard)
     assert np.array_equal(as_np(op), order)
     assert np.array_equal(as_np(ob), bins[order]) and np.array_equal(as_np(oz), z[order])
