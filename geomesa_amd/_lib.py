@@ -198,6 +198,7 @@ SIGNATURES = {
     "gm_z3_histogram": (cint, [vp, vp, vp, vp, i64, cint, cint, cint, cint, cint, vp, vp, vp]),
     "gm_density_points": (cint, [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
     "gm_density_arrow": (cint, [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
+    "gm_density_lines": (cint, [vp, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
     "gm_density_sparse": (cint, [vp, vp, i32, i32, i64, vp, vp, vp, vp]),
     "gm_bin_track": (cint, [vp, vp, i64, vp]),
     "gm_bin_label": (cint, [vp, vp, i64, vp]),

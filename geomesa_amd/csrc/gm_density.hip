@@ -1,4 +1,4 @@
-// gm_density.hip -- the density (heatmap) scan over point features on gfx950.
+// gm_density.hip -- the density (heatmap) scan over point and line features on gfx950.
 //
 // Reference: DensityScan (idx/iterators/DensityScan.scala:29-49, 201-212) renders every feature that passed
 // the scan's filters into a RenderingGrid: RenderingGrid.render(Point, weight)
@@ -23,6 +23,16 @@
 // count falls on its side of DENS_PASS_SHARE x (passes - 1) x n (the call stays stream-ordered).
 // The selection is gm_scan.hpp's RowSel (sel_row per entry, mask_pair per pair of rows; sel_check for the
 // entry points' shared argument errors); gm_density_sparse's count -> scan -> total is its CountScan.
+//
+// Line features (gm_density_lines): RenderingGrid.render(LineString / MultiLineString, weight)
+// (RenderingGrid.scala:72-157) with GridSnap.bresenhamLine (GridSnap.scala:94-126), a lane per segment, in
+// the same kernel with another row loop (line_items) -- the same pixel block, passes, gate and flush.  A
+// segment that leaves the envelope is clipped by the definition of include/geomesa_hip.h, which stands in
+// for JTS's LineString.intersection(envelope): the last-ulp rounding of a crossing and the direction of
+// the clipped piece are parity-unpinned against JTS.  Measured over 1B vertices (tools/
+// density_lines_probe.py, profiles/density_lines_probe.json): device atomics 21.5-29.4 G additions/s, the
+// point scan's rate; one LDS pass 18.6 ms over 20-vertex tracks of 1-3 pixels per step, 34 ms over
+// segments of tens of pixels (261 G additions/s).
 #include <algorithm>
 #include <cmath>
 
@@ -42,7 +52,7 @@ constexpr double DENS_PASS_SHARE = 0.08;   // selected share of the rows at whic
 constexpr uint32_t DENS_THREAD_DRAIN = 1u << 19;
 static_assert((uint64_t)DTPB * DENS_THREAD_DRAIN < (1ull << 32), "thread drain: a counter could wrap");
 
-enum : int { SRC_COLS = 0, SRC_POINT = 1, SRC_MULTI = 2 };
+enum : int { SRC_COLS = 0, SRC_POINT = 1, SRC_MULTI = 2, SRC_LINE = 3 };
 
 struct DensArgs {
   RowSel sel;       // over the rows (columns) or slots (Arrow)
@@ -65,7 +75,10 @@ struct DensSrc {
   const double* y;
   const double* w;      // per row / per slot; unread when unweighted
   ArrowPts pts;
-  const int32_t* o0;    // multipoint: slot -> tuples
+  const int32_t* o0;    // multipoint, linestring: slot -> tuples; multilinestring: slot -> parts
+  const int32_t* o1;    // multilinestring: part -> tuples
+  const uint8_t* bad;   // lines: 1 for a part k_density_line_parts found unrenderable (linestring: part = slot)
+  int multi;            // lines: a multilinestring column
 };
 
 // GridSnap.i / GridSnap.j (GridSnap.scala:60-80): -1 outside [lo, hi], else floor((v - lo) / d).toInt
@@ -114,15 +127,236 @@ __device__ __forceinline__ void render_point(double x, double y, const DensArgs&
   }
 }
 
-// SRC: x / y columns, an Arrow point column or an Arrow multipoint column (F32: Float4 ordinates).
+// ------------------------------------------------------------------ line features
+// RenderingGrid.render(LineString, weight) (RenderingGrid.scala:72-142), one lane per segment.  The
+// segments of a linestring are coupled only through (iN, jN), the last pixel of the nearest earlier
+// in-grid segment, which suppresses the first pixel of the next in-grid one.  That pixel never has to be
+// carried: a walk of more than one pixel ends one major-axis step before its end vertex, so after an
+// in-grid segment the next start pixel (the shared vertex) equals (iN, jN) exactly when that segment
+// stayed in one pixel -- one more vertex to snap.  Only a segment that follows a clipped one looks
+// further back (reenters_last_pixel), walking the vertices behind it until two in a row are in the grid.
+
+// what the reference keeps of a vertex: translate(x) (RenderingGrid.scala:299-330) and GridSnap.j(y)
+struct VSnap {
+  bool ok;      // translate(x) is not empty and j != -1: a segment between two such vertices is in-grid
+  int head;     // translate(x).head, -1 when x came out an ulp below xmin
+  int j;
+  double xup;   // the x of head; widen's further copies are xup + 360, + 360, ... while <= xmax
+};
+
+__device__ __forceinline__ VSnap snap_vertex(double x, double y, const DensArgs& a) {
+  VSnap v{false, -1, grid_snap(y, a.ymin, a.ymax, a.dy, a.rdy, a.height), x};
+  if (x < a.xmin) {
+    v.xup = x + 360.0 * ceil((a.xmin - x) / 360.0);
+    if (v.xup > a.xmax) return v;
+  } else if (x > a.xmax) {
+    v.xup = x - 360.0 * ceil((x - a.xmax) / 360.0);
+    if (v.xup < a.xmin) return v;
+  }
+  if (a.wide) {
+    v.xup = v.xup - 360.0 * floor((v.xup - a.xmin) / 360.0);
+    if (!(v.xup <= a.xmax)) return v;
+  }
+  v.head = grid_snap(v.xup, a.xmin, a.xmax, a.dx, a.rdx, a.width);
+  v.ok = v.j != -1;
+  return v;
+}
+
+// GridSnap.bresenhamLine (GridSnap.scala:94-126): the start pixel alone when both ends share it, else
+// max(dX, dY) pixels from the start, the end pixel left out (take(deltaX), :111, :123).  The minor axis
+// steps by the reference's running FP64 error, replayed as written (for (dX, dY) = (10, 3) it steps a
+// pixel later than the rational walk).  px(i, j) for every pixel but, when skip_first, the first.
+template <class Px>
+__device__ __forceinline__ void bresenham(int x0, int y0, int x1, int y1, bool skip_first, Px px) {
+  const int dX = abs(x1 - x0), dY = abs(y1 - y0);
+  if (dX == 0 && dY == 0) {
+    if (!skip_first) px(x0, y0);
+    return;
+  }
+  const int sx = x0 < x1 ? 1 : -1, sy = y0 < y1 ? 1 : -1;
+  const bool xmajor = dX > dY;
+  const int major = xmajor ? dX : dY;
+  const double de = xmajor ? (double)dY / (double)dX : (double)dX / (double)dY;
+  double err = 0.0;
+  int x = x0, y = y0;
+  for (int k = 0; k < major; ++k) {
+    if (k > 0 || !skip_first) px(x, y);
+    err += de;
+    if (err >= 0.5) {
+      err -= 1.0;
+      x += sx;
+      y += sy;
+    } else if (xmajor) {
+      x += sx;
+    } else {
+      y += sy;
+    }
+  }
+}
+
+// the pixels of an in-grid segment and the start vertex's copies of them (RenderingGrid.scala:107-135):
+// copy k of pixel (i, j) is (i - head + i(xup + 360 k), j); add(i, j) sees columns outside the grid too
+template <class Add>
+__device__ __forceinline__ void draw_segment(const VSnap& p0, const VSnap& p1, bool skip_first, const DensArgs& a,
+                                             Add add) {
+  bresenham(p0.head, p0.j, p1.head, p1.j, skip_first, add);
+  if (!a.wide) return;
+  double xu = p0.xup + 360.0;
+  for (int k = 1; k < a.copies && xu <= a.xmax; ++k) {
+    const int off = grid_snap(xu, a.xmin, a.xmax, a.dx, a.rdx, a.width) - p0.head;
+    bresenham(p0.head, p0.j, p1.head, p1.j, skip_first, [&](int i, int j) { add(i + off, j); });
+    xu += 360.0;
+  }
+}
+
+// vertex t of a line column
+template <bool F32>
+__device__ __forceinline__ VSnap line_vertex(const DensSrc& s, const DensArgs& a, int64_t t) {
+  double x, y;
+  arrow_tuple<F32>(s.pts.c, t, s.pts.flip, x, y);
+  return snap_vertex(x, y, a);
+}
+
+// Segment t (vertices t - 1, t) is in-grid and segment t - 1 was clipped: is (iN, jN) the pixel (i0, j0)
+// of vertex t - 1?  (iN, jN) is the last pixel of the nearest in-grid segment before t - 1 in the part
+// [ps, ..); without one it still is (-1, -1), which no in-grid vertex has.
+template <bool F32>
+__device__ __forceinline__ bool reenters_last_pixel(const DensSrc& s, const DensArgs& a, int64_t ps, int64_t t,
+                                                    int i0, int j0) {
+  VSnap next{false, -1, -1, 0.0};   // vertex m + 1; t - 2 is outside, or segment t - 1 were in-grid
+  for (int64_t m = t - 3; m >= ps; --m) {
+    const VSnap cur = line_vertex<F32>(s, a, m);
+    if (cur.ok && next.ok) {
+      int li = cur.head, lj = cur.j;
+      bresenham(cur.head, cur.j, next.head, next.j, false, [&](int i, int j) { li = i; lj = j; });
+      return li == i0 && lj == j0;
+    }
+    next = cur;
+  }
+  return false;
+}
+
+// One end of the clipped segment a -> b (include/geomesa_hip.h, "the clipped segment"): e itself inside the
+// closed envelope, else its crossing with the vertical side it lies beyond, else with the horizontal one;
+// both ordinates from a, unfused (the unit is built with -ffp-contract=off).  false: no valid crossing.
+__device__ __forceinline__ bool clip_end(double ex, double ey, double ax, double ay, double bx, double by,
+                                         const DensArgs& a, double& ox, double& oy) {
+  if (ex >= a.xmin && ex <= a.xmax && ey >= a.ymin && ey <= a.ymax) { ox = ex; oy = ey; return true; }
+  if (ex < a.xmin || ex > a.xmax) {
+    const double X = ex < a.xmin ? a.xmin : a.xmax;
+    const double y = ay + (X - ax) * ((by - ay) / (bx - ax));
+    if (y >= a.ymin && y <= a.ymax) { ox = X; oy = y; return true; }
+  }
+  if (ey < a.ymin || ey > a.ymax) {
+    const double Y = ey < a.ymin ? a.ymin : a.ymax;
+    const double x = ax + (Y - ay) * ((bx - ax) / (by - ay));
+    if (x >= a.xmin && x <= a.xmax) { ox = x; oy = Y; return true; }
+  }
+  return false;
+}
+
+// segment t (vertices t - 1 -> t, t > ps) of the renderable part that starts at tuple ps
+// (RenderingGrid.scala:85-138); add(i, j) is `pixels(i, j) += weight` before the grid's bounds
+template <bool F32, class Add>
+__device__ __forceinline__ void render_segment(const DensSrc& s, const DensArgs& a, int64_t ps, int64_t t,
+                                               long long& drop, Add add) {
+  double x0, y0, x1, y1;
+  arrow_tuple<F32>(s.pts.c, t - 1, s.pts.flip, x0, y0);
+  arrow_tuple<F32>(s.pts.c, t, s.pts.flip, x1, y1);
+  const VSnap v0 = snap_vertex(x0, y0, a), v1 = snap_vertex(x1, y1, a);
+  const int row_hi = a.row_lo + a.row_n;
+  if (v0.ok && v1.ok) {
+    if (max(v0.j, v1.j) < a.row_lo || min(v0.j, v1.j) >= row_hi) return;   // rows of other passes
+    bool same = false;   // the start pixel is (iN, jN)
+    if (t - 1 > ps) {
+      const VSnap vp = line_vertex<F32>(s, a, t - 2);
+      same = vp.ok ? vp.head == v0.head && vp.j == v0.j : reenters_last_pixel<F32>(s, a, ps, t, v0.head, v0.j);
+    }
+    draw_segment(v0, v1, same, a, add);
+    return;
+  }
+  // RenderingGrid.scala:94-105: the piece of the raw segment inside the closed envelope, rendered as a
+  // fresh Point or two-vertex LineString; (iN, jN) stays
+  if (fmax(x0, x1) < a.xmin || fmin(x0, x1) > a.xmax || fmax(y0, y1) < a.ymin || fmin(y0, y1) > a.ymax) return;
+  double ax, ay, bx, by;
+  if (!clip_end(x0, y0, x0, y0, x1, y1, a, ax, ay) || !clip_end(x1, y1, x0, y0, x1, y1, a, bx, by)) return;
+  if (ax == bx && ay == by) {
+    long long none = 0;
+    render_point(ax, ay, a, none, drop, add);
+  } else {
+    const VSnap c0 = snap_vertex(ax, ay, a), c1 = snap_vertex(bx, by, a);
+    if (c0.ok && c1.ok) draw_segment(c0, c1, false, a, add);
+  }
+}
+
+// The vertices of the selected slots, one per lane.  A wave takes 64 entries of the selection at a time,
+// one per lane, scans their vertex counts and deals the vertices of all of them out 64 at a time, so
+// short linestrings share a wave and a long one spreads over its lanes; a lane finds the slot of its
+// vertex in the scanned counts (6 shuffles) and, in a multilinestring, the part in the slot's offsets.
+// item(slot, part, ps, t): vertex t of the part that starts at tuple ps.  nulls: selected null slots;
+// bad: ids outside [0, n).
+template <int SEL, class Item>
+__device__ __forceinline__ void line_items(const DensSrc& s, const RowSel& sel, long long& nulls, long long& bad,
+                                           Item item) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (DTPB / 64);
+  for (int64_t base = ((int64_t)blockIdx.x * (DTPB / 64) + (threadIdx.x >> 6)) * 64; base < sel.units;
+       base += nwaves * 64) {
+    const int64_t u = base + lane;
+    int64_t r = 0;
+    const int k = u < sel.units ? sel_row<SEL>(sel, u, r) : 0;
+    if (k < 0) ++bad;
+    bool live = k > 0;
+    if (live && !arrow_valid(s.pts.valid, s.pts.voff, r)) { ++nulls; live = false; }
+    int32_t pa = 0, pb = 0;
+    int64_t t0 = 0, cnt = 0;
+    if (live) {
+      pa = s.o0[r];
+      pb = s.o0[r + 1];
+      t0 = s.multi ? s.o1[pa] : pa;
+      cnt = (s.multi ? s.o1[pb] : pb) - t0;
+      if (cnt < 0) cnt = 0;
+    }
+    int64_t inc = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int64_t o = __shfl_up(inc, off, 64);
+      if (lane >= off) inc += o;
+    }
+    const int64_t total = __shfl(inc, 63, 64), first = t0 - (inc - cnt);   // vertex q of the wave is tuple first + q
+    for (int64_t q0 = 0; q0 < total; q0 += 64) {
+      const int64_t q = min(q0 + lane, total - 1);
+      int o = 0;   // the lanes whose scanned count is <= q: the owner of vertex q
+#pragma unroll
+      for (int step = 32; step > 0; step >>= 1)
+        if (__shfl(inc, o + step - 1, 64) <= q) o += step;
+      const int64_t t = __shfl(first, o, 64) + q, rr = __shfl(r, o, 64);
+      int32_t lo = __shfl(pa, o, 64), hi = __shfl(pb, o, 64);
+      if (q0 + lane >= total) continue;
+      if (!s.multi) {
+        item(rr, rr, (int64_t)lo, t);
+      } else {
+        while (hi - lo > 1) {   // the last part that starts at or before t: empty parts start where it does
+          const int32_t m = lo + ((hi - lo) >> 1);
+          if (s.o1[m] <= t) lo = m; else hi = m;
+        }
+        item(rr, (int64_t)lo, (int64_t)s.o1[lo], t);
+      }
+    }
+  }
+}
+
+// SRC: x / y columns, an Arrow point column, an Arrow multipoint column or an Arrow linestring /
+// multilinestring column (F32: Float4 ordinates).
 // SEL: every row, the rows of a mask, or the rows ids names (gm_scan.hpp's RowSel).  LDS: the pass's pixel rows live in LDS
 // (uint32 counters, or FP64 cells when WEIGHTED) and are flushed at the end; else every addition is a
 // device atomic.  VEC (columns, no ids): 16-B pair loads, software-pipelined as k_z3_hist_lds.
 //
 // A uint32 counter cannot wrap: a row adds at most a.copies times, and launch_density sizes the launch so
 // a workgroup sees fewer than 2^31 / copies rows.  A multipoint slot has no such bound (one slot can
-// hold 2^31 tuples), so there a thread that has added DENS_THREAD_DRAIN times drains every counter itself
-// with atomic exchanges: between two exchanges of a counter no thread adds to it more often than that.
+// hold 2^31 tuples), nor has a linestring (it can cross one pixel any number of times), so there a thread
+// that has added DENS_THREAD_DRAIN times drains every counter itself with atomic exchanges: between two
+// exchanges of a counter no thread adds to it more often than that.
 template <int SRC, int SEL, bool WEIGHTED, bool LDS, bool VEC, bool F32>
 __global__ __launch_bounds__(DTPB) void k_density(DensSrc s, DensArgs a, double* __restrict__ grid,
                                                   unsigned long long* __restrict__ tally) {
@@ -146,7 +380,7 @@ __global__ __launch_bounds__(DTPB) void k_density(DensSrc s, DensArgs a, double*
         atomicAdd(&cell[c], w);
       } else {
         atomicAdd(&cnt[c], 1u);
-        if (SRC == SRC_MULTI && ++since == DENS_THREAD_DRAIN) {
+        if ((SRC == SRC_MULTI || SRC == SRC_LINE) && ++since == DENS_THREAD_DRAIN) {
           for (int k = 0; k < total; ++k) {
             const uint32_t v = atomicExch(&cnt[k], 0u);
             if (v) atomicAdd(&gpass[k], (double)v);
@@ -182,7 +416,20 @@ __global__ __launch_bounds__(DTPB) void k_density(DensSrc s, DensArgs a, double*
     }
   };
   const int64_t stride = (int64_t)gridDim.x * DTPB;
-  if constexpr (VEC) {
+  if constexpr (SRC == SRC_LINE) {
+    // RenderingGrid.render(LineString / MultiLineString, weight) (RenderingGrid.scala:72-157): every part
+    // starts afresh; its first vertex has no segment and reports the part when it is unrenderable
+    line_items<SEL>(s, a.sel, skip, bad, [&](int64_t r, int64_t p, int64_t ps, int64_t t) {
+      const bool out = s.bad[p];
+      if (t == ps) skip += out;
+      if (t == ps || out) return;
+      const double w = WEIGHTED ? s.w[r] : 1.0;
+      render_segment<F32>(s, a, ps, t, drop, [&](int i, int j) {
+        if (j < a.row_lo || j >= a.row_lo + a.row_n) return;   // a row of another pass
+        if ((unsigned)i >= (unsigned)a.width) ++drop; else emit(i, j, w);
+      });
+    });
+  } else if constexpr (VEC) {
     const dv2* x2 = (const dv2*)s.x;
     const dv2* y2 = (const dv2*)s.y;
     const dv2* w2 = (const dv2*)s.w;
@@ -262,6 +509,19 @@ __global__ __launch_bounds__(256) void k_density_mask_count(const uint64_t* __re
   if (c) atomicAdd(count, c);
 }
 
+// Marks the parts of the selected slots that the dense grid does not render: any ordinate not finite, or
+// |x| > 2^31 (render_point's rule, for the whole part).  bad[part] is cleared before; lanes that find the
+// same part store the same byte.
+template <int SEL, bool F32>
+__global__ __launch_bounds__(DTPB) void k_density_line_parts(DensSrc s, RowSel sel, uint8_t* __restrict__ bad) {
+  long long nulls = 0, ids = 0;
+  line_items<SEL>(s, sel, nulls, ids, [&](int64_t, int64_t p, int64_t, int64_t t) {
+    double x, y;
+    arrow_tuple<F32>(s.pts.c, t, s.pts.flip, x, y);
+    if (!(fabs(x) <= 2147483648.0) || !(fabs(y) < INFINITY)) bad[p] = 1;
+  });
+}
+
 // pixel rows one LDS pass holds, and the passes a grid takes (DENS_MAX_PASSES + 1: it does not fit)
 inline int dens_rows(const gm_density_grid* g, bool weighted) {
   const int cells = DENS_LDS_BYTES / (weighted ? 8 : 4);
@@ -273,8 +533,9 @@ inline int dens_passes(const gm_density_grid* g, bool weighted) {
   return std::min((g->height + rows - 1) / rows, DENS_MAX_PASSES + 1);
 }
 
+// parts: the parts of a line column (SRC_LINE), for the marks of the unrenderable ones
 int launch_density(gm_ctx* ctx, int src, bool f32, DensSrc s, RowSel rows, const gm_density_grid* g, double* grid,
-                   int64_t* tally) {
+                   int64_t* tally, int64_t parts = 0) {
   DensArgs a;
   a.sel = rows;
   a.xmin = g->xmin; a.ymin = g->ymin; a.xmax = g->xmax; a.ymax = g->ymax;
@@ -309,6 +570,23 @@ int launch_density(gm_ctx* ctx, int src, bool f32, DensSrc s, RowSel rows, const
   const bool vec = src == SRC_COLS && sel != SEL_IDS && aligned16(s.x) && aligned16(s.y) && aligned16(s.w);
   int cus = 256;
   GM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  if (src == SRC_LINE) {   // once per call: every pass and both forms of a gated call read the marks
+    uint8_t* bad;
+    const int rc = tmp.alloc_async((size_t)parts, &bad);
+    if (rc) return rc;
+    GM_HIP(hipMemsetAsync(bad, 0, (size_t)std::max<int64_t>(parts, 1), ctx->stream));
+    s.bad = bad;
+    const int64_t wgs = std::min<int64_t>((int64_t)cus * 2, std::max<int64_t>((units + DTPB - 1) / DTPB, 1));
+    const int prc = with_value<SEL_NONE, SEL_MASK, SEL_IDS>(sel, [&](auto E) {
+      return with_flags([&](auto F) -> int {
+        hipLaunchKernelGGL((k_density_line_parts<E(), F()>), dim3((unsigned)wgs), dim3(DTPB), 0, ctx->stream, s,
+                           a.sel, bad);
+        GM_CHECK_LAUNCH();
+        return GM_OK;
+      }, f32);
+    });
+    if (prc) return prc;
+  }
   auto run = [&](bool in_lds) -> int {
     const int rows = in_lds ? dens_rows(g, weighted) : g->height;
     const int passes = (g->height + rows - 1) / rows;
@@ -331,7 +609,7 @@ int launch_density(gm_ctx* ctx, int src, bool f32, DensSrc s, RowSel rows, const
         return GM_OK;
       };
       // the switches that exist for a source: vector loads for columns, Float4 for Arrow tuples
-      const int rc = with_value<SRC_COLS, SRC_POINT, SRC_MULTI>(src, [&](auto S) {
+      const int rc = with_value<SRC_COLS, SRC_POINT, SRC_MULTI, SRC_LINE>(src, [&](auto S) {
         return with_value<SEL_NONE, SEL_MASK, SEL_IDS>(sel, [&](auto E) {
           return with_flags([&](auto W, auto L, auto V, auto F) {
             if constexpr (S() == SRC_COLS) return go(k_density<SRC_COLS, E(), W(), L(), V() && E() != SEL_IDS, false>);
@@ -463,6 +741,42 @@ int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weig
     f32 = geom->ordinal_bits == 32;
   }
   return launch_density(ctx, src, f32, s, row_sel(n, mask, ids, n_ids), g, grid, tally);
+}
+
+int gm_density_lines(gm_ctx* ctx, const gm_geom_column* geom, const double* weight, int64_t n, const uint64_t* mask,
+                     const int64_t* ids, int64_t n_ids, const gm_density_grid* g, double* grid, int64_t* tally) {
+  const int rc = density_check("gm_density_lines", ctx, n, weight, mask, ids, n_ids, g, grid, tally);
+  if (rc) return rc;
+  if (n == 0 && !ids) return GM_OK;
+  if (n > 0 && (!geom_col_ok(geom) || (geom->type != GM_GEOM_LINESTRING && geom->type != GM_GEOM_MULTILINESTRING))) {
+    set_error("gm_density_lines: geom must be a GM_GEOM_LINESTRING or GM_GEOM_MULTILINESTRING column of 64- or 32-bit "
+              "ordinates");
+    return GM_E_INVALID;
+  }
+  if (ids && n_ids == 0) return GM_OK;
+  GM_HIP(hipSetDevice(ctx->device));
+  DensSrc s{nullptr, nullptr, weight, ArrowPts{nullptr, nullptr, 0, 0, 0}, nullptr, nullptr, nullptr, 0};
+  bool f32 = false;
+  int64_t parts = 0;
+  if (n > 0) {
+    s.pts = ArrowPts{geom->coords, geom->validity, geom->validity_offset, geom->flip_axis, geom->ordinal_bits == 32};
+    s.o0 = geom->offsets[0];
+    s.o1 = geom->offsets[1];
+    s.multi = geom->type == GM_GEOM_MULTILINESTRING;
+    f32 = geom->ordinal_bits == 32;
+    parts = n;
+    if (s.multi) {   // the column's part count is its last slot offset, on the device: the one wait of the call
+      int32_t* last = (int32_t*)ctx->h_pinned;
+      GM_HIP(hipMemcpyAsync(last, s.o0 + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+      GM_HIP(hipStreamSynchronize(ctx->stream));
+      parts = *last;
+      if (parts < 0) {
+        set_error("gm_density_lines: negative slot offset");
+        return GM_E_INVALID;
+      }
+    }
+  }
+  return launch_density(ctx, SRC_LINE, f32, s, row_sel(n, mask, ids, n_ids), g, grid, tally, parts);
 }
 
 int gm_density_sparse(gm_ctx* ctx, const double* grid, int32_t width, int32_t height, int64_t cap, int32_t* i,

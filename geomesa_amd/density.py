@@ -1,11 +1,12 @@
-"""The density (heatmap) scan: point features rendered into a grid of pixels.
+"""The density (heatmap) scan: point and line features rendered into a grid of pixels.
 
 Mirrors DensityScan (geomesa-index-api/.../iterators/DensityScan.scala:29-49, 201-212) over batches of point
 features: every feature the scan kept is snapped into a pixel of a width x height grid over an envelope and
 its weight is added there (RenderingGrid.render, geomesa-utils/.../geotools/RenderingGrid.scala:43-49, with
 GridSnap.i / j, geomesa-utils/.../geotools/GridSnap.scala:60-80, and the 360-degree translate / widen,
-RenderingGrid.scala:299-330).  The per-row work runs in the gm_density_points / gm_density_arrow kernels;
-RenderingGrid keeps the pixels as a dense float64 device tensor.  GridSnap is the host-side class, in numpy
+RenderingGrid.scala:299-330); LineString and MultiLineString features by the Bresenham walk of
+RenderingGrid.scala:72-157 (render_lines, gm_density_lines).  The per-row work runs in the gm_density_points /
+gm_density_arrow / gm_density_lines kernels; RenderingGrid keeps the pixels as a dense float64 device tensor.  GridSnap is the host-side class, in numpy
 float64 with the reference's arithmetic.  The contract, and the three places where the dense grid departs
 from the reference's map of pixels (.skipped, .dropped, .bad_ids), are stated in include/geomesa_hip.h.
 """
@@ -72,10 +73,10 @@ class GridSnap:
 
 
 class RenderingGrid:
-    """RenderingGrid(env, xSize, ySize) for point features (RenderingGrid.scala:25-64), the pixels a dense
+    """RenderingGrid(env, xSize, ySize) for point and line features (RenderingGrid.scala:25-157), the pixels a dense
     float64 [height, width] device tensor; env = (xmin, ymin, xmax, ymax).
 
-    render / render_arrow add a batch; batches add up, and so do the grids of several ranks (any
+    render / render_arrow / render_lines add a batch; batches add up, and so do the grids of several ranks (any
     all-reduce of .grid).  A batch is every row, or the rows a scan or a table query kept:
 
         ids, _, _ = table.query(bboxes, intervals)          # Z3Table, Z2Table, XZ2Table, XZ3Table
@@ -142,6 +143,35 @@ class RenderingGrid:
         cs = col.c_struct()
         check(ctx.lib.gm_density_arrow(ctx.handle, ctypes.byref(cs), ptr(w), n, ptr(mask), ptr(ids), n_ids,
                                        ctypes.byref(g), ptr(self.grid), ptr(self._tally)), "gm_density_arrow")
+        return self
+
+    def render_lines(self, col, weight=None, mask=None, ids=None, kind="linestring", flip_axis=False):
+        """RenderingGrid.render(LineString / MultiLineString, weight) (RenderingGrid.scala:72-157) over an
+        Arrow LineString or MultiLineString column (an arrow.GeometryColumn, or a pyarrow array of `kind`):
+        every pixel of a line's Bresenham walk gets the slot's whole weight; a segment that leaves the
+        envelope is clipped to it (include/geomesa_hip.h states the walk and the clip).  Polygons are not
+        rendered.  The slots a table query kept:
+
+            ids, _, _ = xz2table.query(bboxes)               # XZ2Table / XZ3Table over the same column
+            grid.render_lines(col, ids=ids)
+
+        .skipped counts null slots and parts with a non-finite ordinate or |x| > 2^31, once each."""
+        import torch
+        from .arrow import _as_geom
+        from .curve import _dev_col, _selection
+        col = _as_geom(col, kind, flip_axis)
+        if col.kind not in ("linestring", "multilinestring"):
+            raise ValueError("render_lines renders LineString and MultiLineString columns")
+        n = col.n
+        w = _dev_col(weight, torch.float64) if weight is not None else None
+        if w is not None and w.numel() != n:
+            raise ValueError("weight must have one entry per slot")
+        mask, ids, n_ids = _selection(n, mask, ids, self.grid.device)
+        ctx = _lib.context(self._device)
+        g = self._c()
+        cs = col.c_struct()
+        check(ctx.lib.gm_density_lines(ctx.handle, ctypes.byref(cs), ptr(w), n, ptr(mask), ptr(ids), n_ids,
+                                       ctypes.byref(g), ptr(self.grid), ptr(self._tally)), "gm_density_lines")
         return self
 
     @property

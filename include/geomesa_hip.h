@@ -712,6 +712,63 @@ int gm_density_points(gm_ctx* ctx, const double* x, const double* y, const doubl
    ordinates, either axis order), read in place; weight, mask and ids are per slot. */
 int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weight, int64_t n, const uint64_t* mask,
                      const int64_t* ids, int64_t n_ids, const gm_density_grid* g, double* grid, int64_t* tally);
+/* Line features.  gm_density_points over the n slots of an Arrow GM_GEOM_LINESTRING or
+   GM_GEOM_MULTILINESTRING column (64- or 32-bit ordinates, either axis order), read in place; weight, mask
+   and ids are per slot.  Same grid description, validation, paths and accumulation as gm_density_points
+   (every path valid there for a grid is valid here; an unweighted grid does not depend on path or
+   workgroups); any other geometry type is GM_E_INVALID.  Stream-ordered; a GM_GEOM_MULTILINESTRING call
+   waits for the stream once, to read the column's part count (its last slot offset).
+   Polygons and GeometryCollections are not rendered: the reference fills them with java.awt's fillPolygon
+   (RenderingGrid.scala:189-206), which has no restatement here.
+
+   One linestring with vertices p[0 .. N-1] and weight w is RenderingGrid.render(LineString, weight)
+   (RenderingGrid.scala:72-142) operation for operation; a MultiLineString renders each of its parts so
+   (RenderingGrid.scala:150-157), every part starting afresh.
+     Per vertex: I(p) = translate(p.x) (RenderingGrid.scala:299-330), the list of columns above -- one entry,
+       one per turn for an envelope wider than 360, none when the wrapped x falls outside -- and
+       J(p) = GridSnap.j(p.y) (GridSnap.scala:74-80).
+     State: (iN, jN) = (-1, -1) at the start of the linestring (RenderingGrid.scala:74); segments
+       n = 1 .. N-1 (p0 = p[n-1], p1 = p[n]) are taken in order (RenderingGrid.scala:85-92, 138).
+     In-grid segment (I(p0), I(p1) not empty, J(p0), J(p1) != -1; RenderingGrid.scala:106-135): walk
+       B = GridSnap.bresenhamLine(I(p0).head, J(p0), I(p1).head, J(p1)) (GridSnap.scala:94-126).  B is the
+       single start pixel when both ends share a pixel; otherwise max(dX, dY) pixels from the start pixel,
+       the end pixel left out (take(deltaX), GridSnap.scala:111, 123; GridSnapTest.scala:79-97 pins the
+       lengths 9, 9, 9, 1, 9).  The minor axis steps by the reference's running FP64 error --
+       deltaError = minor.toDouble / major; per pixel error += deltaError, and when error >= 0.5 the minor
+       step is taken and error -= 1 (GridSnap.scala:101-110, 113-122) -- replayed as written: it is not the
+       rational Bresenham ((dX, dY) = (10, 3) steps at x = 6, the rational walk at x = 5).
+       The first pixel of B is written unless it equals (iN, jN) (RenderingGrid.scala:109-115); every later
+       pixel is written (RenderingGrid.scala:120-134).  A write at (i, j) adds w there and at
+       (i - I(p0).head + c, j) for every further entry c of I(p0), the start vertex's copies
+       (RenderingGrid.scala:112-114, 124-126).  Afterwards (iN, jN) is the last pixel of B, written or not
+       (RenderingGrid.scala:116-118, 129-131).  Every written pixel gets the whole w.
+     Clipped segment (any other; RenderingGrid.scala:94-105): the reference renders
+       createLineString(p0, p1).intersection(envelope) (JTS 1.20) as a fresh Point or LineString and leaves
+       (iN, jN) alone.  Here the intersection is defined, on the raw ordinates (no translate), a = p0,
+       b = p1, the rectangle the closed envelope:
+         1. empty when the segment's own envelope misses the rectangle;
+         2. an endpoint inside the closed rectangle is kept bit for bit;
+         3. an endpoint e outside is replaced by a crossing, both ordinates from a, in unfused FP64 in the
+            written order: with the vertical side X (xmin when e.x < xmin, xmax when e.x > xmax),
+            (X, a.y + (X - a.x) * ((b.y - a.y) / (b.x - a.x))), valid when its y lies in [ymin, ymax]; with
+            the horizontal side Y chosen likewise, (a.x + (Y - a.y) * ((b.x - a.x) / (b.y - a.y)), Y), valid
+            when its x lies in [xmin, xmax]; the vertical one when both are valid, empty when none is;
+         4. equal resulting ends are a Point, rendered by render(Point) above (RenderingGrid.scala:43-49);
+         5. unequal ends are the two-vertex linestring a' -> b', in the segment's direction, rendered with
+            a fresh (iN, jN); both ends lie in the envelope, so it is an in-grid segment.
+       Parity-unpinned against JTS: the last-ulp rounding of a crossing (it moves a pixel only within an
+       ulp of a pixel edge) and the direction of the piece (JTS may return b' -> a', which moves the
+       left-out end pixel to the other end) are this definition's, not measured against
+       LineString.intersection.
+   What the dense grid leaves out, in the same tally:
+     tally[0]  parts skipped whole, once per part: a null slot; a linestring part with any non-finite
+               ordinate or any |x| > 2^31 (the other parts of the same MultiLineString still render);
+     tally[1]  additions whose column falls outside [0, width): a -1 column of an ulp-low translate, as
+               for points, and the copies of it;
+     tally[2]  ids outside [0, n).
+   A linestring of 0 or 1 vertices renders nothing and counts nothing. */
+int gm_density_lines(gm_ctx* ctx, const gm_geom_column* geom, const double* weight, int64_t n, const uint64_t* mask,
+                     const int64_t* ids, int64_t n_ids, const gm_density_grid* g, double* grid, int64_t* tally);
 /* The grid as the sparse matrix DensityScan.encodeResult writes (DensityScan.scala:95-106): the cells
    with w != 0.0 into the device arrays i / j / w (cap entries each), ordered by column i, then row j --
    the order encodeResult groups by.  *n_cells (host) receives the cell count; GM_E_CAPACITY when it
