@@ -549,6 +549,42 @@ def test_ranges_failed_query(gpu, oracle, name):
     assert needed.value == len(exp[0]) + len(exp[2])
 
 
+@pytest.mark.parametrize("name", list(RANGES))
+def test_ranges_failed_query_pipelined(gpu, oracle, name):
+    """The batch of test_ranges_failed_query into page-locked output in pipelined chunks of one query
+    (GM_PARAM_RANGES_CHUNK = 1): the failing middle query's status lands in its own slot, the third query's
+    offsets are rebased on the first's total and the failure reaches the return code across chunks.  rc, the
+    statuses, the offsets, *needed and both good lists equal the one-batch pageable call's and the oracle's."""
+    import torch
+    qs, call, orc, code = RANGES[name](oracle)
+    exp = [orc(qs[0]), None, orc(qs[2])]
+    assert exp[0] and exp[2]
+    off1, out1, need1, qst1 = np.full(4, -7, I64), host_ranges(4096), ctypes.c_int64(-7), np.full(3, -7, I32)
+    assert call(gpu.lib, gpu.handle, [0, 1, 2], off1.ctypes.data, out1.ctypes.data, 4096, ctypes.byref(need1),
+                qst1.ctypes.data) == OK
+    total = int(off1[3])
+    assert qst1.tolist() == [0, code, 0] and need1.value == total == len(exp[0]) + len(exp[2])
+    pinned = torch.empty((4096 + 64) * 24, dtype=torch.uint8, pin_memory=True)
+    out = pinned.numpy()
+    gpu.set_param(_lib.GM_PARAM_RANGES_CHUNK, 1)
+    try:
+        for with_status in (True, False):
+            out[:] = FILL
+            out_off, needed, qst = np.full(4, -7, I64), ctypes.c_int64(-7), np.full(3, -7, I32)
+            rc = call(gpu.lib, gpu.handle, [0, 1, 2], out_off.ctypes.data, out.ctypes.data, 4096, ctypes.byref(needed),
+                      qst.ctypes.data if with_status else None)
+            assert rc == (OK if with_status else E_ELEMENT), (name, with_status, rc)
+            if with_status:
+                assert qst.tolist() == [0, code, 0]
+            assert out_off.tolist() == off1.tolist() and needed.value == total, (name, with_status)
+            assert np.array_equal(out[:24 * total], out1[:24 * total]), (name, with_status)
+            for q in (0, 2):
+                assert range_rows(out, int(out_off[q]), int(out_off[q + 1])) == exp[q], (name, with_status, q)
+            assert untouched(out[24 * total:])
+    finally:
+        gpu.set_param(_lib.GM_PARAM_RANGES_CHUNK, 0)
+
+
 @pytest.mark.parametrize("device_out", [False, True])
 @pytest.mark.parametrize("name", list(RANGES))
 def test_ranges_capacity(gpu, oracle, name, device_out):

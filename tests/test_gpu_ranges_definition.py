@@ -1,4 +1,4 @@
-"""The range kernels (gm_ranges.hip) against what a range list must be, and against the oracle where no
+"""The range kernels (gm_ranges_z.hip, gm_ranges_xz.hip) against what a range list must be, and against the oracle where no
 other test varies the parameter.
 
 Sections 1-3 run the kernels under the checkers of ranges_definition.py at the inputs, and with the

@@ -374,8 +374,9 @@ def test_xz_ranges_huge_budget(gpu, oracle, dims, max_ranges):
 
 @pytest.mark.parametrize("dims", [2, 3])
 def test_xz_ranges_many_windows(gpu, oracle, dims):
-    """Queries with more windows than the first pass stages in LDS (16) run again in the second pass
-    with every window in LDS; batched with one-window queries, the output equals the oracle's."""
+    """Queries of 1 to 256 (MAXB) windows in one batch: the one-wave kernel keeps a single window in
+    registers and reads several from the query's normalized windows in its global workspace, looping over
+    them per element; the output equals the oracle's for every query."""
     from geomesa_amd.curve import XZ2SFC, XZ3SFC
     rng = np.random.default_rng(31 + dims)
     qs = []
@@ -423,11 +424,25 @@ def test_xz2_kats_gpu(gpu):  # geomesa-z3/src/test/.../curve/XZ2SFCTest.scala:24
     assert all(hit(rr, int(v)) for v in idx)
 
 
-@pytest.mark.parametrize("kind", ["xz2", "xz3", "z3"])
+def z_raw_entry(oracle, kind, n, seed, mr):
+    """(fn, args, nq, cap, keep-alive arrays) of gm_z2_ranges (`z2`: the boxes of ranges_queries) or
+    gm_zranges with dims 3 (`zranges3`: the Z3 corners of its boxes and intervals)."""
+    from test_gpu_ranges_definition import entry
+    qs = ranges_queries(n, seed=seed)
+    if kind == "z2":
+        qs = [[b] for b, _ in qs]
+    else:
+        z = lambda x, y, t: oracle.z3_index(x, y, t)[1]  # noqa: E731
+        qs = [[(z(b[0], b[1], t[0]), z(b[2], b[3], t[1]))] for b, t in qs]
+    fn, args, keep = entry(kind, qs, mr)
+    return fn, args, n, n * 4096, keep
+
+
+@pytest.mark.parametrize("kind", ["xz2", "xz3", "z3", "z2", "zranges3"])
 def test_ranges_pipelined_chunks(gpu, oracle, kind):
     """Batched ranges into pinned host memory in pipelined query chunks (GM_PARAM_RANGES_CHUNK): the
     chunk results copied back on a second stream while the next chunk runs give exactly the
-    one-batch offsets, ranges and statuses, also through a capacity retry (gm_ranges.hip run_ranges)."""
+    one-batch offsets, ranges and statuses, also through a capacity retry (gm_ranges.hip to_pinned)."""
     import ctypes
     from geomesa_amd import _lib
     from geomesa_amd import ranges as R
@@ -436,6 +451,8 @@ def test_ranges_pipelined_chunks(gpu, oracle, kind):
     if kind == "z3":
         qs = [([b], [(int(t[0]), int(t[1]))]) for b, t in ranges_queries(70, seed=29)]
         fn, args, nq, cap = R.prepare_z3(Z3SFC("week"), qs, 64, 300)
+    elif kind in ("z2", "zranges3"):
+        fn, args, nq, cap, keep = z_raw_entry(oracle, kind, 70, 29, 300)
     else:
         d = 2 if kind == "xz2" else 3
         sfc = XZ2SFC(12) if d == 2 else XZ3SFC(12, "week")
@@ -464,8 +481,8 @@ def test_ranges_pipelined_chunks(gpu, oracle, kind):
         assert got == [(int(a), int(b), bool(c)) for a, b, c in oracle.xz2_ranges(qs[0], max_ranges=300)]
 
 
-@pytest.mark.parametrize("kind", ["z3", "xz2", "xz3"])
-def test_ranges_device_output(gpu, kind):
+@pytest.mark.parametrize("kind", ["z3", "xz2", "xz3", "z2", "zranges3"])
+def test_ranges_device_output(gpu, oracle, kind):
     """Batched ranges written straight into device memory (ranges for a device-side consumer: no copy
     back) equal the host-output batch: offsets, ranges and statuses."""
     import ctypes
@@ -477,6 +494,8 @@ def test_ranges_device_output(gpu, kind):
     if kind == "z3":
         qs = [([b], [(int(t[0]), int(t[1]))]) for b, t in ranges_queries(50, seed=37)]
         fn, args, nq, cap = R.prepare_z3(Z3SFC("week"), qs, 64, 500)
+    elif kind in ("z2", "zranges3"):
+        fn, args, nq, cap, keep = z_raw_entry(oracle, kind, 50, 37, 500)
     else:
         d = 2 if kind == "xz2" else 3
         qs = [[b] if d == 2 else [(b[0], b[1], float(t[0]), b[2], b[3], float(t[1]))]
