@@ -94,13 +94,25 @@ class DensityGrid(ctypes.Structure):
                 ("workgroups", ctypes.c_int32), ("path", ctypes.c_int32)]
 
 
-GM_ATTR_INT32, GM_ATTR_INT64, GM_ATTR_FLOAT64, GM_ATTR_UTF8 = 1, 2, 3, 4
+GM_ATTR_INT32, GM_ATTR_INT64, GM_ATTR_FLOAT64, GM_ATTR_UTF8, GM_ATTR_FLOAT32 = 1, 2, 3, 4, 5
 
 
 class AttrColumn(ctypes.Structure):
     """gm_attr_column: an attribute column gm_bin_track / gm_bin_label read (values, or Utf8 offsets + bytes)."""
     _fields_ = [("type", ctypes.c_int32), ("reserved", ctypes.c_int32), ("values", ctypes.c_void_p),
                 ("offsets", ctypes.c_void_p), ("validity", ctypes.c_void_p), ("validity_offset", ctypes.c_int64)]
+
+
+GM_CMS_MAX_DEPTH = 32
+
+
+class Cms(ctypes.Structure):
+    """gm_cms: a count-min sketch's shape and hash multipliers, the window of time bins its dense block
+    covers, the launch's workgroup count (0 = default) and the path (0 automatic, 1 LDS counters, 2 device
+    atomics)."""
+    _fields_ = [("depth", ctypes.c_int32), ("width", ctypes.c_int32), ("bin_lo", ctypes.c_int32),
+                ("n_bins", ctypes.c_int32), ("workgroups", ctypes.c_int32), ("path", ctypes.c_int32),
+                ("hash_a", ctypes.c_int64 * GM_CMS_MAX_DEPTH)]
 
 
 class BinOpts(ctypes.Structure):
@@ -205,6 +217,10 @@ SIGNATURES = {
     "gm_bin_points": (cint, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]),
     "gm_bin_arrow": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]),
     "gm_bin_sort": (cint, [vp, vp, i64, i32, vp]),
+    "gm_z3_frequency": (cint, [vp, vp, vp, vp, i64, vp, vp, i64, cint, cint, vp, vp, vp, vp]),
+    "gm_frequency_attr": (cint, [vp, vp, vp, i64, vp, vp, i64, cint, cint, vp, vp, vp, vp]),
+    "gm_frequency_points": (cint, [vp, vp, vp, vp, i64, vp, vp, i64, cint, cint, vp, vp, vp, vp]),
+    "gm_cms_estimate": (cint, [vp, vp, vp, vp, vp, i64, vp]),
     "gm_gen_points": (cint, [vp, ctypes.c_uint64, i64, i64, d, d, d, d, i64, i64, vp, vp, vp]),
 }
 

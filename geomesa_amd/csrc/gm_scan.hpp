@@ -2,7 +2,7 @@
 // lane; row_scan: one), the device-wide exclusive scan with its count -> scan -> total helper
 // (CountScan), the row selection of the aggregating scans (RowSel, sel_row) and the mask -> block scan ->
 // ordered compaction pipeline of the filter scans (alloc_scan / finish_scan / end_scan).  Used by
-// gm_filter.hip, gm_geom_filter.hip, gm_pip_query.hip, gm_density.hip and gm_bin.hip.
+// gm_filter.hip, gm_geom_filter.hip, gm_pip_query.hip, gm_density.hip, gm_bin.hip and gm_freq.hip.
 #pragma once
 
 #include "gm_internal.hpp"

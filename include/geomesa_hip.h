@@ -809,6 +809,7 @@ int gm_density_sparse(gm_ctx* ctx, const double* grid, int32_t width, int32_t he
 #define GM_ATTR_INT64 2
 #define GM_ATTR_FLOAT64 3
 #define GM_ATTR_UTF8 4      /* Arrow Utf8: int32 offsets [n + 1] + bytes */
+#define GM_ATTR_FLOAT32 5   /* gm_frequency_attr only; gm_bin_track / gm_bin_label reject it */
 typedef struct {
   int32_t type;              /* GM_ATTR_* */
   int32_t reserved;
@@ -877,6 +878,98 @@ int gm_bin_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* 
    GM_E_INVALID: record_bytes other than 16 / 24; n_records negative or above 2^32 - 1; NULL, misaligned or
    aliased buffers.  Device temporaries: 24 B per record plus gm_sort_keys's. */
 int gm_bin_sort(gm_ctx* ctx, const uint8_t* in, int64_t n_records, int32_t record_bytes, uint8_t* out);
+
+/* ------------------------------------------------------------------ Frequency / Z3Frequency (count-min) */
+/* The two count-min stats of a stats scan (idx/iterators/StatsScan.scala:94-109), which the stats-based cost
+   estimator reads (idx/stats/StatsBasedEstimator.scala:310-324): Frequency
+   (geomesa-utils/.../stats/Frequency.scala) and Z3Frequency (.../stats/Z3Frequency.scala), each a map from a
+   time bin to a CountMinSketch (geomesa-utils/.../clearspring/CountMinSketch.scala).  All integer, 64-bit
+   wrapping as the JVM.
+     The sketch (CountMinSketch.scala:181-203): depth rows of width Long counters and a size; width =
+       ceil(2 / eps).toInt, depth = ceil(-ln(1 - confidence) / ln 2).toInt, hashA(i) =
+       new java.util.Random(-27).nextInt(Int.MaxValue) for i < depth (Frequency.scala:213).  The caller
+       computes the three (the library does no floating point for the sketch); the defaults eps 0.005,
+       confidence 0.95 give width 400, depth 5, hashA 575626169, 278924161, 1519804117, 1200401393, 783957587.
+     hash(item, i) (CountMinSketch.scala:48-57): h = hashA(i) * item, wrapping; h += h >> 32, an arithmetic
+       shift; h &= 2^31 - 1; the bucket is h.toInt % width.
+     add(item, 1) (:59-73): table(i)(hash(item, i)) += 1 for every i < depth, size += 1.
+     estimateCount(item) (:96-105): the minimum over i of table(i)(hash(item, i)).
+     The mask of the curve keys (Frequency.scala:284-287): Long.MaxValue << (64 - precision), precision within
+       0..64; the JVM takes the count mod 64, so precision 0 gives Long.MaxValue, as 64 does.
+   The map of sketches is the dense block table[(bin - bin_lo) * depth * width + i * width + bucket] and
+   size[bin - bin_lo] (device int64) over the time bins bin_lo .. bin_lo + n_bins - 1 -- per bin exactly what
+   a JVM caller copies into sketch.table(i) and sketch._size, and what the serializer writes for a bin with
+   size > 0 (geomesa-utils/.../stats/StatSerializer.scala:487-507, 546-567).  Merging (Frequency.scala:180-187,
+   Z3Frequency.scala:127-131, CountMinSketch.scala:118-135) adds tables and sizes bin by bin; a sketch is a sum
+   of per-row increments, so any row order, workgroup split or rank split gives the same block.
+
+   workgroups, path: as gm_density_grid's.  path 1 = workgroup-private uint32 counters in LDS (depth * width + 1
+   per time bin, 32,768 per pass, as many passes over the rows as the window needs), flushed with one device
+   atomic per nonzero counter; path 2 = one 64-bit device atomic per increment; 0 = automatic: path 1 up to 64
+   passes, path 2 beyond that and when one bin alone does not fit.  The result never depends on either. */
+#define GM_CMS_MAX_DEPTH 32
+typedef struct {
+  int32_t depth, width;          /* 1..GM_CMS_MAX_DEPTH, >= 1 */
+  int32_t bin_lo, n_bins;        /* the window of time bins, as gm_z3_histogram's */
+  int32_t workgroups, path;
+  int64_t hash_a[GM_CMS_MAX_DEPTH];
+} gm_cms;
+
+/* Z3Frequency.observe (Z3Frequency.scala:54-60, 104-115) over rows 0 .. n-1 of the device columns x / y / t_ms:
+   (bin, offset) = BinnedTime(period)(t_ms), z = Z3SFC(period).index(x, y, offset) (not lenient) & mask, and
+   add(z, 1) on that bin's sketch.  Selection (mask / ids / n_ids) exactly as gm_density_points.
+   table, size and tally (device int64[3]) are accumulated into and never cleared, and the call is
+   stream-ordered: batches, and the blocks of several ranks, add.
+     tally[0]  rows skipped because the reference's toKey throws (a date BinnedTime rejects, a point outside
+               the curve's bounds; Z3Frequency logs a warning and moves on) or an ordinate is NaN (which fails
+               the bounds check; gm_arrow_points_to_columns writes NaN for null slots, so this is also the
+               null rule of x / y columns);
+     tally[1]  rows whose time bin lies outside the window: not added, so a caller can widen the window and
+               run the new bins alone, as with gm_z3_histogram.  A row counts in tally[0] before it can here;
+     tally[2]  entries of ids outside [0, n), skipped and never read through.
+   Pointers need 8-B alignment; x, y and t_ms all 16-B aligned take the vector-load kernel.
+   GM_E_INVALID, with a gm_last_error text: a NULL ctx, cms, table, size or tally; a column NULL with n > 0;
+   n < 0; an unknown period; depth outside 1..GM_CMS_MAX_DEPTH; width < 1; n_bins < 1; a window outside the
+   Short range (bin_lo < -32768 or bin_lo + n_bins > 32768); n_bins * depth * width > 2^31 - 1; the selection
+   errors of gm_density_points (n_ids < 0, mask and ids both given); path outside 0..2, or path 1 when one
+   bin's depth * width + 1 counters exceed 32,768; workgroups < 0; precision outside 0..64; a misaligned
+   pointer. */
+int gm_z3_frequency(gm_ctx* ctx, const double* x, const double* y, const int64_t* t_ms, int64_t n,
+                    const uint64_t* mask, const int64_t* ids, int64_t n_ids, int period, int precision,
+                    const gm_cms* cms, int64_t* table, int64_t* size, int64_t* tally);
+/* Frequency.observe (Frequency.scala:159-168) of an attribute column.  The time bin is
+   BinnedTime(period)(dtg).bin, and Frequency.DefaultTimeBin = 0 without a dtg column (NULL) or at a null
+   date slot.  The key by the column's type (Frequency.scala:302-306):
+     GM_ATTR_INT32    (long)(v / precision): Int division, truncating toward zero (-7 / 2 = -3)
+     GM_ATTR_INT64    v / precision: Long division (java.lang.Long, and a Date as its epoch milliseconds)
+     GM_ATTR_FLOAT32  Math.round(v * (float)precision): the float32 product, then the closest int
+     GM_ATTR_FLOAT64  Math.round(v * (double)precision): the FP64 product, then the closest long
+   Math.round takes ties toward +Infinity (-0.5 -> 0, 2.5 -> 3, 0.49999999999999994 -> 0), maps NaN to 0 and
+   saturates; the product is not fused with anything.  A null attribute slot is not observed and counts
+   nowhere.  Frequency.observe has no try: a date BinnedTime rejects makes the reference's scan throw; here
+   the row is skipped and counted in tally[0].  tally[1], tally[2], selection, accumulation and the errors as
+   gm_z3_frequency (precision there aside); also GM_E_INVALID: a NULL col; GM_ATTR_UTF8 (a string key hashes
+   through com.clearspring's MurmurHash, which the reference tree does not hold) and unknown types; an
+   integer column with precision < 1 (0 throws in the reference; negative divisors are not reproduced);
+   values or millis NULL with n > 0 or not naturally aligned.  8-byte columns whose values and millis are
+   16-B aligned take the vector-load kernel; 4-byte columns always take scalar loads. */
+int gm_frequency_attr(gm_ctx* ctx, const gm_attr_column* col, const gm_time_column* dtg, int64_t n,
+                      const uint64_t* mask, const int64_t* ids, int64_t n_ids, int period, int precision,
+                      const gm_cms* cms, int64_t* table, int64_t* size, int64_t* tally);
+/* Frequency.observe of a point geometry attribute (Frequency.scala:289-293): the key is
+   Z2SFC.index(x, y) (not lenient) & mask, the time bin as gm_frequency_attr's.  The reference throws for a
+   point outside the curve's bounds; here the row is skipped and counted in tally[0], as is a NaN ordinate
+   and a rejected date.  Everything else as gm_z3_frequency. */
+int gm_frequency_points(gm_ctx* ctx, const double* x, const double* y, const gm_time_column* dtg, int64_t n,
+                        const uint64_t* mask, const int64_t* ids, int64_t n_ids, int period, int precision,
+                        const gm_cms* cms, int64_t* table, int64_t* size, int64_t* tally);
+/* estimateCount of n keys (device int64), one lane per key, into out (device int64).  bins NULL: the sum over
+   the window's sketches -- Frequency.count(value), countDirect(value) (Frequency.scala:78, 117-118); else
+   (device int16, as gm_z3_index_key writes them) the estimate in bins[i]'s sketch, 0 for a bin outside the
+   window (:87, :128-129; Z3Frequency.scala:81).  Stream-ordered.  GM_E_INVALID: a NULL ctx, cms or table;
+   n < 0; the sketch and window errors above; keys or out NULL with n > 0; a misaligned pointer. */
+int gm_cms_estimate(gm_ctx* ctx, const gm_cms* cms, const int64_t* table, const int64_t* keys, const int16_t* bins,
+                    int64_t n, int64_t* out);
 
 /* ------------------------------------------------------------------ synthetic data (bench/tests) */
 /* SplitMix64 keyed by (seed, index): lon U[lon0,lon1), lat U[lat0,lat1), t_ms U[t0,t1).  Each of x, y and
