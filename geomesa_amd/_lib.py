@@ -281,9 +281,27 @@ class Context:
         check(lib.gm_ctx_create(device, ctypes.c_void_p(stream), ctypes.byref(self._h)), "gm_ctx_create")
         self.lib = lib
 
+    @classmethod
+    def owned(cls, device=0):
+        """A context on a new non-blocking stream of its own (gm_ctx_create_owned); `stream` names it."""
+        import torch
+        lib = load()
+        if not torch.cuda.is_available():
+            raise GeomesaHipUnavailable("no GPU visible: the geomesa_amd product path needs a MI355X")
+        torch.cuda.set_device(device)
+        self = cls.__new__(cls)
+        self.device, self.lib, self._h = device, lib, ctypes.c_void_p()
+        check(lib.gm_ctx_create_owned(device, ctypes.byref(self._h)), "gm_ctx_create_owned")
+        return self
+
     @property
     def handle(self):
         return self._h
+
+    @property
+    def stream(self):
+        """The hipStream_t every call of this context launches on, as an integer (0 = the null stream)."""
+        return self.lib.gm_ctx_stream(self._h) or 0
 
     def set_param(self, param, value):
         check(self.lib.gm_ctx_set_param(self._h, int(param), int(value)), "gm_ctx_set_param")

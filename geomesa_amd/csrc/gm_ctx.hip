@@ -146,7 +146,7 @@ int hip_fail(hipError_t e, const char* what) {
 
 int begin_summary(gm_ctx* ctx, gm_batch_status* summary) {
   if (!summary) return GM_OK;
-  const int64_t init[2] = {0, INT64_MAX};
+  static const int64_t init[2] = {0, INT64_MAX};   // static: nothing here waits for the copy
   GM_HIP(hipMemcpyAsync(ctx->d_err, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
   return GM_OK;
 }

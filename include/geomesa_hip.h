@@ -26,6 +26,9 @@
  *    query_status == NULL and some query has a non-zero status.  Offsets, ranges and *needed are
  *    still delivered, and GM_E_CAPACITY takes precedence when both apply.
  *  - Thread safety: one gm_ctx per thread; calls on different contexts are independent.
+ *  - Asynchrony: beside the entry points whose own comment says asynchronous or stream-ordered, these only
+ *    enqueue work on the context's stream and return: gm_z3_invert, gm_z2_invert, gm_legacy_z3_invert,
+ *    gm_legacy_z2_invert, gm_z3_key_bytes, gm_z2_key_bytes, gm_arrow_points_to_columns, gm_gen_points.
  *  - Configuration knobs the Scala code reads from system properties
  *    (geomesa.scan.ranges.target, geomesa.scan.ranges.recurse, XZ precision g, ...) are
  *    explicit parameters here, never globals.
@@ -252,7 +255,13 @@ int gm_xz3_ranges(gm_ctx* ctx, int64_t n_queries, const int32_t* win_off, const 
    ids_cap is written, and ids != NULL with ids_cap < 0 is GM_E_INVALID).
    *n_match (host) receives the match count (this call synchronises when n_match != NULL);
    GM_E_CAPACITY when ids is given and the matches exceed ids_cap.  The same output rules hold for
-   every scan below. */
+   every scan below.
+   Waits.  The four scans that take filter_bytes (this one, gm_z2filter_scan and the two _rows forms) wait
+   for the context stream once before their kernel is launched, whatever n_match is: the filter's
+   descriptor is uploaded from pageable host memory and that copy is waited for.  With n_match == NULL
+   they return without waiting for their own kernels; gm_strict_scan, and gm_query_scan without a geometry
+   term, do not wait at all then.  gm_query_scan with a geometry term always synchronises (it reports its
+   reference check itself). */
 int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const int16_t* bin_ranges,
                      int n_bin_ranges, const int16_t* bin, const int64_t* z, int64_t n, uint64_t* mask,
                      int64_t* ids, int64_t ids_cap, int64_t* n_match);
@@ -496,7 +505,8 @@ int gm_z2_key_bytes(gm_ctx* ctx, const uint8_t* shard, const int64_t* z, int64_t
    then bin as an unsigned big-endian short, then z as an unsigned big-endian long (what Accumulo /
    HBase keep sorted).  Stable; perm_out[i] = the input row of table row i.  shard / shard_out may
    be NULL together (unsharded table); bin / bin_out may be NULL together (a key space without a time
-   bin: Z2, XZ2).  n < 2^32.  Device temporaries: about 32.5 B per row (+ 4 B without a bin). */
+   bin: Z2, XZ2).  n < 2^32.  Device temporaries: about 32.5 B per row (+ 4 B without a bin).
+   Synchronises the context stream: the sort's plan reads the keys' varying bits back. */
 int gm_sort_keys(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
                  uint8_t* shard_out, int16_t* bin_out, int64_t* z_out, int64_t* perm_out);
 
@@ -876,7 +886,8 @@ int gm_bin_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* 
    into out (device, another buffer).  A concatenation of sorted batches comes out as their merge
    (BinSorter.mergeSort, BinSorter.scala:85-145), so the batches of several ranks combine through it.
    GM_E_INVALID: record_bytes other than 16 / 24; n_records negative or above 2^32 - 1; NULL, misaligned or
-   aliased buffers.  Device temporaries: 24 B per record plus gm_sort_keys's. */
+   aliased buffers.  Device temporaries: 24 B per record plus gm_sort_keys's.  Synchronises the
+   context stream, as gm_sort_keys. */
 int gm_bin_sort(gm_ctx* ctx, const uint8_t* in, int64_t n_records, int32_t record_bytes, uint8_t* out);
 
 /* ------------------------------------------------------------------ Frequency / Z3Frequency (count-min) */

@@ -82,3 +82,30 @@ def test_header_constants_match_binding():
     assert len(defs) >= 12
     for k, v in defs.items():
         assert getattr(_lib, k) == v, k
+
+
+def test_every_entry_point_has_a_stream_case():
+    """Every symbol of _lib.SIGNATURES is in the case table of tests/stream_order.py (which test_gpu_streams.py
+    runs on a caller's stream) or in its exclusion list, with one written reason; never in both.  A new entry
+    point fails here until it gets a case."""
+    import stream_order as SO
+    covered = SO.covered_entries()
+    assert covered <= set(_lib.SIGNATURES), covered - set(_lib.SIGNATURES)
+    assert not covered & set(SO.EXCLUDED), covered & set(SO.EXCLUDED)
+    assert set(SO.EXCLUDED) <= set(_lib.SIGNATURES) and all(r.strip() for r in SO.EXCLUDED.values())
+    missing = sorted(set(_lib.SIGNATURES) - covered - set(SO.EXCLUDED))
+    assert not missing, missing
+    allowed = ("context lifecycle", "parameters", "alloc / free", "thread-local text", "a constant", "the timers",
+               "index destroy", "index stats", "the census")
+    assert all(r.startswith(allowed) for r in SO.EXCLUDED.values())
+    for name, (entries, waits, _) in SO.TABLE.items():
+        assert isinstance(waits, bool) and name.split("[")[0].split("+")[0] in entries + ("gm_pip_index_transfer",), name
+
+
+def test_every_stream_case_has_a_distinct_decoy():
+    """The references of a case's true and decoy datasets differ in more than half of their elements (rows, mask
+    words, counters non-zero in either), so a kernel that read the decoy cannot pass; computed on the CPU."""
+    import stream_order as SO
+    for name in SO.TABLE:
+        share = SO.decoy_share(name)
+        assert share is None or share > 0.5, (name, share)

@@ -595,3 +595,43 @@ def test_invalid_sources_and_alignment(gpu):
     assert same(G.read(np.float64).reshape(16, 16), want) and T.read(np.int64).tolist() == tally.tolist()
     for b in (X, Y, G, T):
         b.check("valid call")
+
+
+def test_two_abi_calls_of_gm_density_arrow_into_one_grid_add_up(gpu):
+    """gm_density_arrow twice into one grid and tally, two different POINT batches of two blocks and an odd tail,
+    nothing waited for in between: each batch alone equals its reference, and the shared grid equals the sum of
+    both references."""
+    from geomesa_amd import _lib
+    from geomesa_amd.arrow import GeomColumnC
+    env, px, n = ENV_OF_GRID[(256, 256)], 256, N_BLOCKS
+    g = grid_c(env, px, px)
+    pts = [random_points(env, n, 1500 + seed) for seed in (0, 1)]
+    for seed, (x, y) in enumerate(pts):
+        x[seed::41 + seed] = np.nan         # the tallies add up too
+    refs = [R.render_numpy(env, px, px, x, y) for x, y in pts]
+    assert all(r[0].sum() > 1000 and r[1].any() for r in refs) and not same(refs[0][0], refs[1][0])
+    YX = [Guarded.of(np.stack([y, x], 1).reshape(-1)) for x, y in pts]
+    cols = [GeomColumnC(0, 64, 0, 0, b.addr, None, 0, (ctypes.c_void_p * 3)(None, None, None)) for b in YX]
+
+    def fresh():
+        G, T = Guarded(px * px * 8), Guarded(24)
+        G.write(np.zeros(px * px)); T.write(np.zeros(3, np.int64))
+        return G, T
+
+    def render(col, G, T):
+        assert gpu.lib.gm_density_arrow(gpu.handle, ctypes.byref(col), None, n, None, None, 0, ctypes.byref(g), G.ptr,
+                                        T.ptr) == _lib.GM_OK, _lib.last_error()
+
+    for k, (col, (want, tally)) in enumerate(zip(cols, refs)):
+        G, T = fresh()
+        render(col, G, T)
+        gpu.sync()
+        assert same(G.read(np.float64).reshape(px, px), want) and T.read(np.int64).tolist() == tally.tolist(), k
+    G, T = fresh()
+    render(cols[0], G, T)
+    render(cols[1], G, T)
+    gpu.sync()
+    assert same(G.read(np.float64).reshape(px, px), refs[0][0] + refs[1][0])
+    assert T.read(np.int64).tolist() == (refs[0][1] + refs[1][1]).tolist()
+    for buf in YX + [G, T]:
+        buf.check("two calls")

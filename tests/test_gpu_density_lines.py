@@ -468,3 +468,59 @@ def test_a_valid_call_writes_grid_and_tally_only(gpu, multi):
     assert tally[2] == 2 and want.sum() > 0
     for b in (YX, OFF, SLOT, W, I, G, T):
         b.check("valid call")
+
+
+TWO_CALL_ENV, TWO_CALL_PX = (-1.0, 33.0, 6.0, 40.0), 64
+TWO_CALL_LINES = 2 * 1024 + 6      # one lane per segment: 3 x 2054 = 6 blocks of 1024 lanes + 18; even: slots pair up
+
+
+def two_call_batch(seed, multi):
+    """2054 lines of 4 vertices over the envelope and a margin of a tenth of it, two lines per slot if multi:
+    (column, its buffers, slots, rows as the reference takes them)."""
+    env, n = TWO_CALL_ENV, TWO_CALL_LINES
+    rng = np.random.default_rng(1300 + seed)
+    mx, my = 0.1 * (env[2] - env[0]), 0.1 * (env[3] - env[1])
+    x = rng.uniform(env[0] - mx, env[2] + mx, 4 * n)
+    y = rng.uniform(env[1] - my, env[3] + my, 4 * n)
+    x[-8 + seed::4] = np.nan           # the last two lines cannot be rendered: the tallies add up too
+    YX, OFF = Guarded.of(np.stack([y, x], 1).reshape(-1)), Guarded.of((4 * np.arange(n + 1)).astype(np.int32))
+    rows = [[(float(x[4 * r + v]), float(y[4 * r + v])) for v in range(4)] for r in range(n)]
+    if not multi:
+        return c_column(1, YX, [OFF]), [YX, OFF], n, rows
+    SLOT = Guarded.of((2 * np.arange(n // 2 + 1)).astype(np.int32))
+    return c_column(4, YX, [SLOT, OFF]), [YX, OFF, SLOT], n // 2, [rows[2 * r:2 * r + 2] for r in range(n // 2)]
+
+
+@pytest.mark.parametrize("multi", [False, True], ids=["linestring", "multilinestring"])
+def test_two_abi_calls_into_one_grid_add_up(gpu, multi):
+    """gm_density_lines twice into one grid and tally, two different batches, nothing waited for in between:
+    each batch alone equals its reference, and the shared grid equals the sum of both references."""
+    from geomesa_amd import _lib
+    px = TWO_CALL_PX
+    g = grid_c(TWO_CALL_ENV, px, px)
+    batches = [two_call_batch(seed, multi) for seed in (0, 1)]
+    refs = [L.render_lines_numpy(TWO_CALL_ENV, px, px, b[3]) for b in batches]
+    assert all(r[0].sum() > 10000 and r[1].any() for r in refs) and not same(refs[0][0], refs[1][0])
+
+    def fresh():
+        G, T = Guarded(px * px * 8), Guarded(24)
+        G.write(np.zeros(px * px)); T.write(np.zeros(3, np.int64))
+        return G, T
+
+    def render(b, G, T):
+        assert gpu.lib.gm_density_lines(gpu.handle, ctypes.byref(b[0]), None, b[2], None, None, 0, ctypes.byref(g), G.ptr,
+                                        T.ptr) == _lib.GM_OK, _lib.last_error()
+
+    for k, (b, (want, tally)) in enumerate(zip(batches, refs)):
+        G, T = fresh()
+        render(b, G, T)
+        gpu.sync()
+        assert same(G.read(np.float64).reshape(px, px), want) and T.read(np.int64).tolist() == tally.tolist(), k
+    G, T = fresh()
+    render(batches[0], G, T)
+    render(batches[1], G, T)
+    gpu.sync()
+    assert same(G.read(np.float64).reshape(px, px), refs[0][0] + refs[1][0])
+    assert T.read(np.int64).tolist() == (refs[0][1] + refs[1][1]).tolist()
+    for buf in batches[0][1] + batches[1][1] + [G, T]:
+        buf.check("two calls")
