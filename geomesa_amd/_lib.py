@@ -36,6 +36,8 @@ GM_PARAM_INDEX_CORE_RETIRED = 7
 GM_PARAM_HIST_GRID = 8
 GM_PARAM_RELATE_ROWS64 = 9
 
+GM_GEOM_WKB = 16
+
 GM_JOIN_AUTO = 0
 GM_JOIN_DIRECT = 1
 GM_SPATIAL_NONE, GM_SPATIAL_INTERSECTS, GM_SPATIAL_CONTAINS = 0, 1, 2

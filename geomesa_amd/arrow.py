@@ -8,7 +8,10 @@ hands such vectors to the C-ABI without building per-feature JTS objects:
   * LineStringVector, MultiPointVector -- List<FixedSizeList(2)> (AbstractLineStringVector.java);
   * PolygonVector, MultiLineStringVector -- List<List<FixedSizeList(2)>>, rings shell first
     (AbstractPolygonVector.java:56-84);
-  * MultiPolygonVector -- List<List<List<FixedSizeList(2)>>> (AbstractMultiPolygonVector.java:61-95).
+  * MultiPolygonVector -- List<List<List<FixedSizeList(2)>>> (AbstractMultiPolygonVector.java:61-95);
+  * WKBGeometryVector -- Binary, one JTS WKB blob per slot, any class in any slot: what a geom:Geometry
+    attribute is written as (WKBGeometryVector.java:27-93).  Kind "wkb": envelopes, XZ keys, the exact box
+    filter of the XZ tables and points_to_columns read it; the blob grammar is in geomesa_hip.h.
 
 A pyarrow Array of one of those shapes becomes a GeometryColumn: its buffers are copied to HBM once
 (the stand-in for the JVM handing over off-heap Arrow buffers that already live on the device) and
@@ -28,7 +31,8 @@ from . import _lib
 from ._lib import ALLOW_ELEMENT as _ELEMENT, check, ptr
 from .curve import IllegalArgumentException, TimePeriod, _raise_first, _summary
 
-KINDS = {"point": 0, "linestring": 1, "polygon": 2, "multipoint": 3, "multilinestring": 4, "multipolygon": 5}
+KINDS = {"point": 0, "linestring": 1, "polygon": 2, "multipoint": 3, "multilinestring": 4, "multipolygon": 5,
+         "wkb": 16}
 LEVELS = {"point": 0, "linestring": 1, "multipoint": 1, "polygon": 2, "multilinestring": 2, "multipolygon": 3}
 
 
@@ -76,13 +80,31 @@ def _tuples(fsl):
     return flat[start:start + 2 * len(fsl)], bits
 
 
+def _wkb_values(arr):
+    """(value bytes, int32 value offsets with the array offset applied, n + 1 entries) of a Binary array."""
+    import pyarrow as pa
+    if pa.types.is_large_binary(arr.type):
+        raise IllegalArgumentException("a WKB column must be Arrow Binary: LargeBinary has int64 offsets, the "
+                                       "gm_geom_column int32")
+    if not pa.types.is_binary(arr.type):
+        raise IllegalArgumentException("expected an Arrow Binary column of WKB blobs, got %s" % arr.type)
+    _, obuf, data = arr.buffers()
+    offs = np.frombuffer(obuf, np.int32)[arr.offset:arr.offset + len(arr) + 1] if obuf is not None else \
+        np.zeros(1, np.int32)
+    return (np.frombuffer(data, np.uint8) if data is not None else np.zeros(0, np.uint8)), offs
+
+
 def arrow_buffers(arr, kind):
     """The buffers a gm_geom_column points at, host side: (ordinates, ordinal bits, validity bitmap or
-    None, validity bit offset, [List offsets, outermost first])."""
+    None, validity bit offset, [List offsets, outermost first]).  Kind "wkb": the value bytes, 64 and the
+    value offsets."""
     kind = kind.lower()
     if kind not in KINDS:
         raise IllegalArgumentException("unknown geometry kind %r" % kind)
     valid, voff = _validity(arr)
+    if kind == "wkb":
+        data, offs = _wkb_values(arr)
+        return data, 64, valid, voff, [offs]
     offs = []
     level = arr
     for _ in range(LEVELS[kind]):
@@ -173,6 +195,9 @@ def _as_time(col):
     return TimeColumn(col)
 
 
+_WKB_POINTS = "; points_to_columns gives a WKB column's points as x / y columns for the point entries"
+
+
 def _finish(st, what, status_t, outs):
     if status_t is not None:
         return outs + (status_t,)
@@ -191,7 +216,7 @@ def z3_index_keys(points, dtg=None, period=TimePeriod.Week, lenient=False, statu
     g = _as_geom(points, "point", flip_axis)
     t = _as_time(dtg)
     if g.kind != "point":
-        raise IllegalArgumentException("Z3 keys index point geometries")
+        raise IllegalArgumentException("Z3 keys index point geometries" + _WKB_POINTS * (g.kind == "wkb"))
     n = g.n
     ctx = _lib.context()
     dev = g._coords.device
@@ -211,7 +236,7 @@ def z2_index_keys(points, lenient=False, status=False, flip_axis=False):
     import torch
     g = _as_geom(points, "point", flip_axis)
     if g.kind != "point":
-        raise IllegalArgumentException("Z2 keys index point geometries")
+        raise IllegalArgumentException("Z2 keys index point geometries" + _WKB_POINTS * (g.kind == "wkb"))
     n = g.n
     ctx = _lib.context()
     z = torch.empty(n, dtype=torch.int64, device=g._coords.device)
@@ -259,10 +284,14 @@ def xz3_index_keys(geoms, dtg=None, kind="polygon", g=12, period=TimePeriod.Week
     return _finish(st, "XZ3IndexKeySpace.toIndexKey", s, (b, xz))
 
 
-def points_to_columns(points, flip_axis=False):
-    """(x, y) float64 device columns of an Arrow point column; null points are NaN."""
+def points_to_columns(points, flip_axis=False, kind="point"):
+    """(x, y) float64 device columns of an Arrow point column; null points are NaN.  Of a "wkb" column: the
+    slots whose top-level geometry is a Point; every other slot (null, malformed, the empty point, any other
+    class) is NaN."""
     import torch
-    g = _as_geom(points, "point", flip_axis)
+    g = _as_geom(points, kind, flip_axis)
+    if g.kind not in ("point", "wkb"):
+        raise IllegalArgumentException("points_to_columns reads a point or a WKB column")
     n = g.n
     ctx = _lib.context()
     xy = torch.empty(2 * max(n, 1), dtype=torch.float64, device=g._coords.device)

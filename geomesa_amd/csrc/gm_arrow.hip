@@ -14,6 +14,7 @@
 
 #include "gm_arrow.hpp"
 #include "gm_keys.hpp"
+#include "gm_wkb.hpp"
 
 namespace gm {
 
@@ -208,22 +209,47 @@ __global__ __launch_bounds__(ATPB) void k_points_soa(ArrowPts g, int64_t n, doub
   }
 }
 
+// the adapter over a GM_GEOM_WKB column: x, y of a slot whose top-level geometry is a Point; a null or
+// malformed slot, the empty point (a NaN ordinate) and every other class are NaN, NaN
+__global__ __launch_bounds__(ATPB) void k_points_soa_wkb(ArrowGeom g, int64_t n, double* __restrict__ x,
+                                                         double* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * ATPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * ATPB) {
+    double px = NAN, py = NAN;
+    if (arrow_valid(g.valid, g.voff, i)) {
+      WkbCur c = wkb_slot(g, i);
+      WkbHead h;
+      const uint8_t* t;
+      if (wkb_head<false>(c, h) && h.code == WKB_POINT && wkb_run(c, 1, h.stride, t)) {
+        WkbTuples{t, h.stride, h.le}.tuple(0, px, py);
+        if (px != px || py != py) px = py = NAN;
+      }
+    }
+    x[i] = px;
+    y[i] = py;
+  }
+}
+
 // ------------------------------------------------------------------ envelopes (XZ keys)
 // (Env, ArrowGeom and geom_envelope: gm_arrow.hpp)
 
-// XZ2IndexKeySpace / XZ3IndexKeySpace.toIndexKey over an Arrow geometry column; DIM 3 also bins the date
-template <int DIM, int PERIOD, bool LENIENT, bool F32>
+// XZ2IndexKeySpace / XZ3IndexKeySpace.toIndexKey over an Arrow geometry column; DIM 3 also bins the date.
+// WKB: a GM_GEOM_WKB column (F32 false), a malformed slot keyed as a null one
+template <int DIM, int PERIOD, bool LENIENT, bool F32, bool WKB>
 __global__ __launch_bounds__(ATPB) void k_xz_key_arrow(ArrowGeom g, ArrowTime tc, int64_t n, int gp, double zhi,
                                                        int16_t* __restrict__ bin, int64_t* __restrict__ xz,
                                                        uint8_t* __restrict__ status, int64_t* __restrict__ err) {
+  __shared__ uint32_t s_rem[WKB ? WKB_DEPTH * ATPB : 1];   // wkb_walk's stack, one column per lane
   for (int64_t i = (int64_t)blockIdx.x * ATPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * ATPB) {
     int64_t out = 0;
     int16_t b = 0;
     uint8_t st;
-    if (!arrow_valid(g.valid, g.voff, i)) {
+    Env e;
+    bool valid = arrow_valid(g.valid, g.voff, i);
+    if (WKB) valid = valid && wkb_envelope(g, i, s_rem + threadIdx.x, ATPB, e);
+    if (!valid) {
       st = ST_NULL_GEOM;
     } else {
-      const Env e = geom_envelope<F32>(g, i);
+      if (!WKB) e = geom_envelope<F32>(g, i);
       if (DIM == 2) {
         st = xz2_one<LENIENT>(gp, e.minx, e.miny, e.maxx, e.maxy, out);
       } else {
@@ -287,9 +313,16 @@ void launch_z3_arrow(hipStream_t s, bool vec, ArrowPts g, ArrowTime tc, int64_t 
 template <int DIM, int PERIOD>
 void launch_xz_arrow(hipStream_t s, bool lenient, bool f32, ArrowGeom g, ArrowTime tc, int64_t n, int gp, double zhi,
                      int16_t* bin, int64_t* xz, uint8_t* status, int64_t* err) {
+  if (g.type == GM_GEOM_WKB) {
+    with_flags([&](auto L) {
+      hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, L(), false, true>), dim3(agrid(n)), dim3(ATPB), 0, s, g, tc, n,
+                         gp, zhi, bin, xz, status, err);
+    }, lenient);
+    return;
+  }
   with_flags([&](auto L, auto F) {
-    hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, L(), F()>), dim3(agrid(n)), dim3(ATPB), 0, s, g, tc, n, gp, zhi,
-                       bin, xz, status, err);
+    hipLaunchKernelGGL((k_xz_key_arrow<DIM, PERIOD, L(), F(), false>), dim3(agrid(n)), dim3(ATPB), 0, s, g, tc, n, gp,
+                       zhi, bin, xz, status, err);
   }, lenient, f32);
 }
 
@@ -302,6 +335,7 @@ extern "C" {
 int gm_z3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* dtg, int64_t n, int period,
                           int lenient, int16_t* bin, int64_t* z, uint8_t* status, gm_batch_status* summary) {
   if (!ctx || n < 0 || !valid_period(period)) return GM_E_INVALID;
+  if (rejects_wkb(geom, "gm_z3_index_key_arrow", true)) return GM_E_INVALID;
   if (n == 0) return empty_batch(summary);
   if (!point_col_ok(geom) || !bin || !z) return GM_E_INVALID;
   GM_HIP(hipSetDevice(ctx->device));
@@ -323,6 +357,7 @@ int gm_z3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time
 int gm_z2_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, int lenient, int64_t* z, uint8_t* status,
                           gm_batch_status* summary) {
   if (!ctx || n < 0) return GM_E_INVALID;
+  if (rejects_wkb(geom, "gm_z2_index_key_arrow", true)) return GM_E_INVALID;
   if (n == 0) return empty_batch(summary);
   if (!point_col_ok(geom) || !z) return GM_E_INVALID;
   GM_HIP(hipSetDevice(ctx->device));
@@ -377,6 +412,15 @@ int gm_xz3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_tim
 int gm_arrow_points_to_columns(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, double* x, double* y) {
   if (!ctx || n < 0) return GM_E_INVALID;
   if (n == 0) return GM_OK;
+  if (geom && geom->type == GM_GEOM_WKB) {
+    if (!geom_col_ok(geom) || !x || !y) return GM_E_INVALID;
+    GM_HIP(hipSetDevice(ctx->device));
+    const ArrowGeom ag{geom->coords, geom->validity, geom->validity_offset, geom->offsets[0], nullptr, nullptr,
+                       geom->type, 0};
+    hipLaunchKernelGGL(k_points_soa_wkb, dim3(agrid(n)), dim3(ATPB), 0, ctx->stream, ag, n, x, y);
+    GM_CHECK_LAUNCH();
+    return GM_OK;
+  }
   if (!point_col_ok(geom) || !x || !y) return GM_E_INVALID;
   GM_HIP(hipSetDevice(ctx->device));
   const ArrowPts g = to_pts(geom);
@@ -392,6 +436,7 @@ int gm_arrow_points_to_columns(gm_ctx* ctx, const gm_geom_column* geom, int64_t 
 int gm_pip_index_create_arrow(gm_ctx* ctx, const gm_geom_column* polys, int32_t n, int cells_per_poly,
                               gm_pip_index** out) {
   if (!ctx || !out || n < 0 || !polys) return GM_E_INVALID;
+  if (rejects_wkb(polys, "gm_pip_index_create_arrow", false)) return GM_E_INVALID;
   if (polys->type != GM_GEOM_POLYGON && polys->type != GM_GEOM_MULTIPOLYGON) return GM_E_INVALID;
   if (n > 0 && !geom_col_ok(polys)) return GM_E_INVALID;
   const bool multi = polys->type == GM_GEOM_MULTIPOLYGON;

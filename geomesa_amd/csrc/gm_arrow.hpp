@@ -3,7 +3,8 @@
 // (AbstractPointVector.java:52-79, AbstractPolygonVector.java:72-79); Float4 vectors
 // (PointFloatVector, ...FloatVector) widen their floats to double on read (readOrdinal).  Also the nested
 // geometry column as a kernel argument (ArrowGeom) and its JTS envelope walk (Env, geom_envelope), shared by
-// the XZ key kernels (gm_arrow.hip) and the geometry full filter (gm_geom_filter.hip).
+// the XZ key kernels (gm_arrow.hip) and the geometry full filter (gm_geom_filter.hip).  A GM_GEOM_WKB column
+// travels in the same ArrowGeom (c: the value bytes, o0: the value offsets) and is read by gm_wkb.hpp only.
 #pragma once
 
 #include "gm_internal.hpp"
@@ -143,10 +144,20 @@ inline int offset_levels(int type) {
 
 inline bool geom_col_ok(const gm_geom_column* g) {
   if (!g || !g->coords || (g->ordinal_bits != 64 && g->ordinal_bits != 32)) return false;
+  if (g->type == GM_GEOM_WKB) return g->ordinal_bits == 64 && g->offsets[0];   // value bytes, value offsets
   const int lv = offset_levels(g->type);
   if (lv < 0) return false;
   for (int k = 0; k < lv; ++k)
     if (!g->offsets[k]) return false;
+  return true;
+}
+
+// The entries that read typed columns only: true (and the gm_last_error text) for a GM_GEOM_WKB column.
+// A point entry names the adapter that takes such a column's points to x / y columns.
+inline bool rejects_wkb(const gm_geom_column* g, const char* who, bool point_entry) {
+  if (!g || g->type != GM_GEOM_WKB) return false;
+  set_error(std::string(who) + ": a GM_GEOM_WKB column is not read here" +
+            (point_entry ? "; gm_arrow_points_to_columns gives its points as x / y columns" : ""));
   return true;
 }
 

@@ -606,6 +606,7 @@ int gm_bin_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_time_column* 
   const int rc = bin_check(who, ctx, n, track, label, mask, ids, n_ids, o, out, cap, n_records, tally);
   if (rc) return rc;
   if ((date_off == nullptr) != (dates == nullptr)) return bin_fail(who, "date_off and dates come together");
+  if (rejects_wkb(geom, who, true)) return GM_E_INVALID;
   if (geom && geom->type != GM_GEOM_POINT && geom->type != GM_GEOM_LINESTRING)
     return bin_fail(who, "geom must be a GM_GEOM_POINT or GM_GEOM_LINESTRING column");
   if (geom && geom->type == GM_GEOM_POINT && dates) return bin_fail(who, "a date list needs a GM_GEOM_LINESTRING column");

@@ -724,6 +724,7 @@ int gm_density_arrow(gm_ctx* ctx, const gm_geom_column* geom, const double* weig
                      const int64_t* ids, int64_t n_ids, const gm_density_grid* g, double* grid, int64_t* tally) {
   const int rc = density_check("gm_density_arrow", ctx, n, weight, mask, ids, n_ids, g, grid, tally);
   if (rc) return rc;
+  if (rejects_wkb(geom, "gm_density_arrow", true)) return GM_E_INVALID;
   if (n == 0 && !ids) return GM_OK;
   if (n > 0 && (!geom_col_ok(geom) || (geom->type != GM_GEOM_POINT && geom->type != GM_GEOM_MULTIPOINT))) {
     set_error("gm_density_arrow: geom must be a GM_GEOM_POINT or GM_GEOM_MULTIPOINT column of 64- or 32-bit ordinates");
@@ -747,6 +748,7 @@ int gm_density_lines(gm_ctx* ctx, const gm_geom_column* geom, const double* weig
                      const int64_t* ids, int64_t n_ids, const gm_density_grid* g, double* grid, int64_t* tally) {
   const int rc = density_check("gm_density_lines", ctx, n, weight, mask, ids, n_ids, g, grid, tally);
   if (rc) return rc;
+  if (rejects_wkb(geom, "gm_density_lines", false)) return GM_E_INVALID;
   if (n == 0 && !ids) return GM_OK;
   if (n > 0 && (!geom_col_ok(geom) || (geom->type != GM_GEOM_LINESTRING && geom->type != GM_GEOM_MULTILINESTRING))) {
     set_error("gm_density_lines: geom must be a GM_GEOM_LINESTRING or GM_GEOM_MULTILINESTRING column of 64- or 32-bit "

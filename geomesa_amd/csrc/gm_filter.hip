@@ -864,8 +864,10 @@ int gm_table_scan_geom(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, co
   if (!geom) return set_error("gm_table_scan_geom: the geometry column is required"), GM_E_INVALID;
   if (geom->ordinal_bits != 64 && geom->ordinal_bits != 32)
     return set_error("gm_table_scan_geom: ordinal_bits must be 64 or 32"), GM_E_INVALID;
-  if (geom->type < GM_GEOM_POINT || geom->type > GM_GEOM_MULTIPOLYGON)
+  if ((geom->type < GM_GEOM_POINT || geom->type > GM_GEOM_MULTIPOLYGON) && geom->type != GM_GEOM_WKB)
     return set_error("gm_table_scan_geom: unknown geometry type"), GM_E_INVALID;
+  if (geom->type == GM_GEOM_WKB && geom->ordinal_bits != 64)
+    return set_error("gm_table_scan_geom: ordinal_bits must be 64 for a GM_GEOM_WKB column"), GM_E_INVALID;
   if (!geom_col_ok(geom))
     return set_error("gm_table_scan_geom: coords or a List offsets level of the geometry type is NULL"), GM_E_INVALID;
   return table_scan(ctx, shard, bin, z, n, ranges, n_ranges, f, geom, perm, ids, ids_cap, n_match, n_scanned,

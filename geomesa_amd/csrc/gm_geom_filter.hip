@@ -29,6 +29,7 @@
 #include "gm_arrow.hpp"
 #include "gm_pip.hpp"
 #include "gm_scan.hpp"
+#include "gm_wkb.hpp"
 
 namespace gm {
 
@@ -79,15 +80,25 @@ __device__ __forceinline__ int32_t uoff(const int32_t* __restrict__ o, int64_t i
   return __builtin_amdgcn_readfirstlane(o[i]);
 }
 
-// the tuples [a, b) as points: some point in the box
+// the tuples of a typed column as a tuple source (a WKB run is the other one: WkbTuples, gm_wkb.hpp)
 template <bool F32>
-__device__ bool points_meet(const ArrowGeom& g, int32_t a, int32_t b, int lane, const Box& q) {
+struct ArrowTuples {
+  const void* c;
+  int flip;
+  __device__ __forceinline__ void tuple(int64_t j, double& x, double& y) const { arrow_tuple<F32>(c, j, flip, x, y); }
+};
+template <bool F32>
+__device__ __forceinline__ ArrowTuples<F32> tuples_of(const ArrowGeom& g) { return ArrowTuples<F32>{g.c, g.flip}; }
+
+// the tuples [a, b) as points: some point in the box
+template <class SRC>
+__device__ bool points_meet(const SRC& g, int32_t a, int32_t b, int lane, const Box& q) {
   for (int32_t j0 = a; j0 < b; j0 += 64) {
     const int32_t j = j0 + lane;
     bool h = false;
     if (j < b) {
       double x, y;
-      arrow_tuple<F32>(g.c, j, g.flip, x, y);
+      g.tuple(j, x, y);
       h = pt_in_box(x, y, q);
     }
     if (__any(h)) return true;
@@ -99,13 +110,13 @@ __device__ bool points_meet(const ArrowGeom& g, int32_t a, int32_t b, int lane, 
 // step reads one contiguous run of 64 tuples, one per lane, and takes each segment's second end from the
 // next lane, so a step covers 63 segments and no tuple is loaded twice within it.  RING also counts the
 // crossings of the corner (q.x0, q.y0) (on a segment: a hit) and gives the ring's parity
-template <bool F32, bool RING>
-__device__ bool line_meets(const ArrowGeom& g, int32_t a, int32_t b, int lane, const Box& q, bool& inside) {
+template <bool RING, class SRC>
+__device__ bool line_meets(const SRC& g, int32_t a, int32_t b, int lane, const Box& q, bool& inside) {
   int cross = 0;
   for (int32_t j0 = a; j0 < b - 1; j0 += 63) {
     const int32_t j = j0 + lane;
     double ax = 0.0, ay = 0.0;
-    if (j < b) arrow_tuple<F32>(g.c, j, g.flip, ax, ay);
+    if (j < b) g.tuple(j, ax, ay);
     const double bx = __shfl_down(ax, 1, 64), by = __shfl_down(ay, 1, 64);
     bool h = false;
     if (lane < 63 && j < b - 1) {
@@ -120,13 +131,13 @@ __device__ bool line_meets(const ArrowGeom& g, int32_t a, int32_t b, int lane, c
 
 // the rings [r0, r1) of `ro` as one polygon, shell first: a ring segment meets the box, or the box's
 // corner is inside the shell and inside no hole (SimplePointInAreaLocator.locatePointInPolygon)
-template <bool F32>
-__device__ bool polygon_meets(const ArrowGeom& g, const int32_t* __restrict__ ro, int32_t r0, int32_t r1, int lane,
+template <class SRC>
+__device__ bool polygon_meets(const SRC& g, const int32_t* __restrict__ ro, int32_t r0, int32_t r1, int lane,
                               const Box& q) {
   bool in_shell = false, in_hole = false;
   for (int32_t r = r0; r < r1; ++r) {
     bool in = false;
-    if (line_meets<F32, true>(g, uoff(ro, r), uoff(ro, r + 1), lane, q, in)) return true;
+    if (line_meets<true>(g, uoff(ro, r), uoff(ro, r + 1), lane, q, in)) return true;
     if (r == r0) in_shell = in; else in_hole |= in;
   }
   return in_shell && !in_hole;
@@ -136,6 +147,7 @@ __device__ bool polygon_meets(const ArrowGeom& g, const int32_t* __restrict__ ro
 template <bool F32>
 __device__ bool geom_meets_box(const ArrowGeom& g, int64_t i, int lane, const Box& q) {
   bool unused;
+  const ArrowTuples<F32> ts = tuples_of<F32>(g);
   switch (g.type) {
     case GM_GEOM_POINT: {
       double x, y;
@@ -143,45 +155,89 @@ __device__ bool geom_meets_box(const ArrowGeom& g, int64_t i, int lane, const Bo
       return pt_in_box(x, y, q);
     }
     case GM_GEOM_MULTIPOINT:
-      return points_meet<F32>(g, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
+      return points_meet(ts, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
     case GM_GEOM_LINESTRING:
-      return line_meets<F32, false>(g, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q, unused);
+      return line_meets<false>(ts, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q, unused);
     case GM_GEOM_POLYGON:
-      return polygon_meets<F32>(g, g.o1, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
+      return polygon_meets(ts, g.o1, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
     case GM_GEOM_MULTILINESTRING: {
       const int32_t l1 = uoff(g.o0, i + 1);
       for (int32_t l = uoff(g.o0, i); l < l1; ++l)
-        if (line_meets<F32, false>(g, uoff(g.o1, l), uoff(g.o1, l + 1), lane, q, unused)) return true;
+        if (line_meets<false>(ts, uoff(g.o1, l), uoff(g.o1, l + 1), lane, q, unused)) return true;
       return false;
     }
     default: {   // GM_GEOM_MULTIPOLYGON
       const int32_t p1 = uoff(g.o0, i + 1);
       for (int32_t p = uoff(g.o0, i); p < p1; ++p)
-        if (polygon_meets<F32>(g, g.o2, uoff(g.o1, p), uoff(g.o1, p + 1), lane, q)) return true;
+        if (polygon_meets(ts, g.o2, uoff(g.o1, p), uoff(g.o1, p + 1), lane, q)) return true;
       return false;
     }
   }
 }
 
-template <bool F32>
+// A WKB slot against the box, the whole wave on one slot (wkb_walk<true>): each class decided as
+// geom_meets_box decides it, a collection by any of its elements; the walk stops at the first hit.  A
+// LineString of one tuple is that point.  A MultiPoint's points each carry a header of their own, so they
+// are taken one per step, every lane alike.
+struct WkbMeets {
+  Box q;
+  int lane;
+  bool in_shell, in_hole;
+  __device__ __forceinline__ bool point(const WkbTuples& t) {
+    double x, y;
+    t.tuple(0, x, y);
+    return pt_in_box(x, y, q);
+  }
+  __device__ __forceinline__ bool line(const WkbTuples& t, uint32_t n) {
+    bool unused;
+    return n == 1 ? point(t) : line_meets<false>(t, 0, (int32_t)n, lane, q, unused);
+  }
+  __device__ __forceinline__ void polygon_begin() { in_shell = in_hole = false; }
+  __device__ __forceinline__ bool ring(uint32_t r, const WkbTuples& t, uint32_t n) {
+    bool in = false;
+    if (line_meets<true>(t, 0, (int32_t)n, lane, q, in)) return true;
+    if (r == 0) in_shell = in; else in_hole |= in;
+    return false;
+  }
+  __device__ __forceinline__ bool polygon_end() { return in_shell && !in_hole; }
+};
+
+// WKB: the column is GM_GEOM_WKB (F32 false).  The shortcuts go by the slot's top-level code; a malformed
+// slot never matches (its envelope column holds the null envelope, so it is not even walked)
+template <bool F32, bool WKB>
 __global__ __launch_bounds__(GTPB) void k_geom_refine(ArrowGeom g, GeomRefine a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t nwaves = (int64_t)gridDim.x * (GTPB / 64);
-  const bool connected = g.type == GM_GEOM_LINESTRING || g.type == GM_GEOM_POLYGON;
+  bool connected = g.type == GM_GEOM_LINESTRING || g.type == GM_GEOM_POLYGON;
+  __shared__ uint32_t s_rem[WKB ? WKB_DEPTH * (GTPB / 64) : 1];   // wkb_walk's stack, one column per wave
   for (int64_t s = (int64_t)blockIdx.x * (GTPB / 64) + wave; s < a.n_surv; s += nwaves) {
     const int64_t c = a.surv[s];
     const int64_t row = cand_row(a.coff, a.start, a.nr, c);
     const int64_t r = a.rows ? a.rows[row] : row;
     bool hit = false;
-    if (arrow_valid(g.valid, g.voff, r)) {
+    bool valid = arrow_valid(g.valid, g.voff, r);
+    if (WKB && valid) {
+      WkbCur top = wkb_slot(g, r);
+      WkbHead h;
+      valid = wkb_head<true>(top, h);
+      connected = valid && (h.code == WKB_LINESTRING || h.code == WKB_POLYGON);
+    }
+    if (valid) {
       const double ex0 = a.xmin[r], ey0 = a.ymin[r], ex1 = a.xmax[r], ey1 = a.ymax[r];
       for (int k = 0; k < a.nbox && !hit; ++k) {
         const double* b = a.boxes + 4 * k;
         if (!env_intersects(ex0, ey0, ex1, ey1, b)) continue;
         const Box q{b[0], b[1], b[2], b[3]};
         const bool xin = ex0 >= q.x0 && ex1 <= q.x1, yin = ey0 >= q.y0 && ey1 <= q.y1;
-        hit = (xin && yin) || (connected && (xin || yin)) || geom_meets_box<F32>(g, r, lane, q);
+        hit = (xin && yin) || (connected && (xin || yin));
+        if (hit) continue;
+        if (WKB) {
+          WkbMeets v{q, lane, false, false};
+          hit = wkb_walk<true>(wkb_slot(g, r), s_rem + wave, GTPB / 64, v) == WKB_STOP;
+        } else {
+          hit = geom_meets_box<F32>(g, r, lane, q);
+        }
       }
     }
     if (!hit && lane == 0) atomicAnd((unsigned long long*)&a.mask[c >> 6], ~(1ull << (c & 63)));
@@ -215,6 +271,21 @@ __global__ __launch_bounds__(GTPB) void k_arrow_envelopes(ArrowGeom g, int64_t n
   }
 }
 
+// the same over a GM_GEOM_WKB column: one lane walks one slot's bytes (gm_wkb.hpp)
+__global__ __launch_bounds__(GTPB) void k_wkb_envelopes(ArrowGeom g, int64_t n, double* __restrict__ xmin,
+                                                        double* __restrict__ ymin, double* __restrict__ xmax,
+                                                        double* __restrict__ ymax) {
+  __shared__ uint32_t s_rem[WKB_DEPTH * GTPB];
+  for (int64_t i = (int64_t)blockIdx.x * GTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GTPB) {
+    Env e = env_null();
+    if (arrow_valid(g.valid, g.voff, i)) wkb_envelope(g, i, s_rem + threadIdx.x, GTPB, e);
+    xmin[i] = e.minx;
+    ymin[i] = e.miny;
+    xmax[i] = e.maxx;
+    ymax[i] = e.maxy;
+  }
+}
+
 static ArrowGeom to_geom(const gm_geom_column* c) {
   return ArrowGeom{c->coords, c->validity, c->validity_offset, c->offsets[0], c->offsets[1], c->offsets[2], c->type,
                    c->flip_axis};
@@ -223,9 +294,13 @@ static ArrowGeom to_geom(const gm_geom_column* c) {
 int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a) {
   const ArrowGeom g = to_geom(geom);
   const int64_t blocks = std::min<int64_t>((a.n_surv + GTPB / 64 - 1) / (GTPB / 64), 1 << 20);
-  with_flags([&](auto F) {
-    hipLaunchKernelGGL((k_geom_refine<F()>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, a);
-  }, geom->ordinal_bits == 32);
+  if (geom->type == GM_GEOM_WKB) {
+    hipLaunchKernelGGL((k_geom_refine<false, true>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, a);
+  } else {
+    with_flags([&](auto F) {
+      hipLaunchKernelGGL((k_geom_refine<F(), false>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, a);
+    }, geom->ordinal_bits == 32);
+  }
   GM_CHECK_LAUNCH();
   const int64_t nblocks = (a.total + FROWS - 1) / FROWS;
   hipLaunchKernelGGL(k_mask_recount, dim3((unsigned)nblocks), dim3(64), 0, ctx->stream, a.mask, a.total, a.counts);
@@ -247,10 +322,15 @@ int gm_arrow_envelopes(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, doubl
   GM_HIP(hipSetDevice(ctx->device));
   const ArrowGeom g = to_geom(geom);
   const int64_t blocks = std::min<int64_t>((n + GTPB - 1) / GTPB, 256 * 32);
-  with_flags([&](auto F) {
-    hipLaunchKernelGGL((k_arrow_envelopes<F()>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, n, xmin, ymin,
-                       xmax, ymax);
-  }, geom->ordinal_bits == 32);
+  if (geom->type == GM_GEOM_WKB) {
+    hipLaunchKernelGGL(k_wkb_envelopes, dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, n, xmin, ymin, xmax,
+                       ymax);
+  } else {
+    with_flags([&](auto F) {
+      hipLaunchKernelGGL((k_arrow_envelopes<F()>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, n, xmin,
+                         ymin, xmax, ymax);
+    }, geom->ordinal_bits == 32);
+  }
   GM_CHECK_LAUNCH();
   return GM_OK;
 }

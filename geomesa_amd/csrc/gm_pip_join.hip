@@ -676,6 +676,7 @@ int gm_pip_join_arrow(gm_ctx* ctx, const gm_pip_index* ix, const gm_geom_column*
                       int64_t* pt_ids, int32_t* poly_ids, int64_t cap, int64_t* n_pairs, int mode, int predicate) {
   if (!ctx || !ix || n < 0 || cap < 0 || !pts) return GM_E_INVALID;
   if (predicate != GM_SPATIAL_CONTAINS && predicate != GM_SPATIAL_INTERSECTS) return GM_E_INVALID;
+  if (rejects_wkb(pts, "gm_pip_join_arrow", true)) return GM_E_INVALID;
   if (pts->type != GM_GEOM_POINT || (pts->ordinal_bits != 64 && pts->ordinal_bits != 32)) return GM_E_INVALID;
   if (n > 0 && !pts->coords) return GM_E_INVALID;
   if ((pt_ids == nullptr) != (poly_ids == nullptr)) return GM_E_INVALID;

@@ -432,14 +432,56 @@ int gm_pip_relate(gm_ctx* ctx, const gm_pip_index* index, const int32_t* poly, c
 #define GM_GEOM_MULTIPOINT 3      /* offsets[0]: slot -> tuples */
 #define GM_GEOM_MULTILINESTRING 4 /* offsets[0]: slot -> lines, offsets[1]: line -> tuples */
 #define GM_GEOM_MULTIPOLYGON 5    /* offsets[0]: slot -> polygons, [1]: polygon -> rings, [2]: ring -> tuples */
+/* The seventh vector: WKBGeometryVector (geomesa-arrow-jts WKBGeometryVector.java:27-93), what an
+   attribute declared geom:Geometry is written as (geomesa-arrow-gt ArrowAttributeWriter.scala:266-267; read
+   at ArrowAttributeReader.scala:432 and through GeometryFields.java:40).  An Arrow Binary column, one JTS
+   WKBWriter blob per slot, any geometry class in any slot.  As a gm_geom_column:
+     coords        the Binary value buffer (bytes, any alignment)
+     offsets[0]    the int32 value offsets, n + 1 entries: slot i is bytes [offsets[0][i], offsets[0][i+1]);
+                   offsets[1], offsets[2] unused
+     validity, validity_offset   as for the typed columns
+     ordinal_bits  64 (WKB ordinates are doubles); anything else is GM_E_INVALID
+     flip_axis     ignored: WKB is always x then y (the vector stores its flipAxisOrder flag but never
+                   applies it to the bytes, WKBGeometryVector.java:66-75, 122-129)
+   The blob grammar -- the OGC / ISO WKB layout plus the EWKB flag bits -- is this rule, and the rule is
+   the definition.  JTS is outside the reference tree, so agreement with JTS 1.20's WKBReader itself is
+   PARITY UNPINNED.
+     geometry := order:u8 (0 = big-endian, 1 = little-endian; anything else is malformed)
+                 typeInt:u32 in that order
+                 [srid:u32 if typeInt & 0x20000000]   (skipped)
+                 body
+     code = (typeInt & 0xffff) % 1000          iso = (typeInt & 0xffff) / 1000
+     hasZ = typeInt & 0x80000000 or iso in {1, 3};  hasM = typeInt & 0x40000000 or iso in {2, 3}
+     tuple = (2 + hasZ + hasM) doubles; x, y are the first two; Z and M are skipped
+     1 Point            one tuple; a NaN x or y = the empty point
+     2 LineString       count:u32, count tuples
+     3 Polygon          rings:u32, each ring count:u32 + tuples; ring 0 is the shell
+     4 MultiPoint / 5 MultiLineString / 6 MultiPolygon / 7 GeometryCollection
+                        count:u32, then count complete geometries, each with its own order byte and
+                        typeInt; an element of a Multi* must have the matching single code
+   Each nested geometry carries its own byte order and orders may differ inside one blob (JTS's own
+   writer emits big-endian 2-D blobs without SRID: POINT (0 20) is 00 00000001 0000000000000000
+   4034000000000000).  Collections (codes 4 .. 7) nest to at most GM_WKB_MAX_DEPTH levels; that is this
+   library's limit.  Bytes after the top-level geometry are ignored.  Ordinates are read as 64-bit
+   patterns: NaN payloads and -0.0 arrive as written.
+   A MALFORMED SLOT IS TREATED EXACTLY AS A NULL SLOT.  A slot is malformed when the order byte or the
+   code is unknown, when a header or a tuple run would end past the slot's end, when a Multi* element has
+   the wrong code, or when collections nest deeper than the limit (WKBGeometryVector.get throws there,
+   WKBGeometryVector.java:78-92; the entries below have no per-slot error channel besides the key entries'
+   status).  No byte outside [offsets[0][i], offsets[0][i+1]) is read, whatever the headers claim.
+   Entries that take the type: gm_arrow_envelopes, gm_xz2_index_key_arrow, gm_xz3_index_key_arrow,
+   gm_arrow_points_to_columns, gm_table_scan_geom.  Every other entry with a gm_geom_column argument
+   returns GM_E_INVALID for it (gm_last_error names the type). */
+#define GM_GEOM_WKB 16
+#define GM_WKB_MAX_DEPTH 8
 
 typedef struct {
   int32_t type;              /* GM_GEOM_* */
-  int32_t ordinal_bits;      /* 64 (Float8 vectors) or 32 (Float4 "...FloatVector"s) */
+  int32_t ordinal_bits;      /* 64 (Float8 vectors, WKB) or 32 (Float4 "...FloatVector"s) */
   int32_t flip_axis;         /* 0: [y, x] tuples (the default), 1: [x, y] */
   int32_t reserved;
   const void* coords;        /* tuple ordinates, tuple j at [2j], [2j + 1] (already advanced by the
-                                innermost child array's offset) */
+                                innermost child array's offset); GM_GEOM_WKB: the value bytes */
   const uint8_t* validity;   /* top-level validity bitmap, NULL = no nulls */
   int64_t validity_offset;   /* bit index of slot 0 in validity (the Arrow array offset) */
   const int32_t* offsets[3]; /* List offsets, outermost first, each advanced by its array's offset;
@@ -472,10 +514,15 @@ int gm_xz3_index_key_arrow(gm_ctx* ctx, const gm_geom_column* geom, const gm_tim
                            int period, int lenient, int16_t* bin, int64_t* xz, uint8_t* status,
                            gm_batch_status* summary);
 /* Geometry.getEnvelopeInternal of every slot as four device columns (a null slot and an empty geometry:
-   the JTS null envelope, 0, 0, -1, -1): the envelope columns of gm_scan_filter.  Asynchronous. */
+   the JTS null envelope, 0, 0, -1, -1): the envelope columns of gm_scan_filter.  Asynchronous.
+   GM_GEOM_WKB: a collection's envelope is the merge of its elements', null ones skipped; a malformed slot
+   reads as a null slot.  The two XZ key entries above index the same envelope (GM_ST_NULL_GEOM for a null
+   or malformed slot, GM_ST_UNORDERED for an empty geometry). */
 int gm_arrow_envelopes(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, double* xmin, double* ymin,
                        double* xmax, double* ymax);
-/* A point column as x / y device columns (null slots -> NaN): the adapter for every other entry */
+/* A point column as x / y device columns (null slots -> NaN): the adapter for every other entry.
+   GM_GEOM_WKB: x, y of a slot whose top-level geometry is a Point; a null or malformed slot, the empty
+   point and every other class (a one-element MultiPoint included) are NaN, NaN. */
 int gm_arrow_points_to_columns(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, double* x, double* y);
 /* gm_pip_join_pred over an Arrow point column (null points never match): the direct pass reads the
    tuples in place */
@@ -618,7 +665,10 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
    slot is found as its envelope is: f->rows, else perm, else the identity.  *n_envelope (host, optional)
    receives the candidates that pass the row filter, during and the envelope test -- gm_table_scan's *n_match
    for the same arguments.  ids, ids_cap, *n_match, *n_scanned, GM_E_CAPACITY and the synchronisation are
-   gm_table_scan's. */
+   gm_table_scan's.
+   A GM_GEOM_WKB slot (ordinal_bits 64, coords and offsets[0]) is decided per class in the same way: a
+   collection matches iff any element does, a LineString of one tuple is that point, and a malformed slot
+   never matches -- its envelope column holds the null envelope, which is what keeps it from the walk. */
 int gm_table_scan_geom(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
                        const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
                        const gm_geom_column* geom, const int64_t* perm, int64_t* ids, int64_t ids_cap,
