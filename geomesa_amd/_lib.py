@@ -13,6 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GEOMESA_HIP_LIB", os.path.join(HERE, "lib", "libgeomesa_hip.so"))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "geomesa_hip.h")
 
+GM_ABI_VERSION = 2   # the header's; 2: gm_scan_filter.polys
+GM_POLY_QUERY_MAX_VERTICES = 65536
+
 GM_OK = 0
 GM_E_INVALID = -1
 GM_E_HIP = -2
@@ -74,7 +77,7 @@ class ScanFilter(ctypes.Structure):
                 ("xmin", ctypes.c_void_p), ("ymin", ctypes.c_void_p), ("xmax", ctypes.c_void_p),
                 ("ymax", ctypes.c_void_p), ("boxes", ctypes.c_void_p), ("n_boxes", ctypes.c_int32),
                 ("during", ctypes.c_int32), ("t_ms", ctypes.c_void_p), ("t_lo", ctypes.c_int64),
-                ("t_hi", ctypes.c_int64), ("rows", ctypes.c_void_p)]
+                ("t_hi", ctypes.c_int64), ("rows", ctypes.c_void_p), ("polys", ctypes.c_void_p)]
 
 
 # numpy view of gm_key_range rows (24 B, the KeyRange layout)

@@ -710,7 +710,8 @@ int gm_strict_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t*
 
 // gm_table_scan and gm_table_scan_geom: the seek, the mask pass and the compaction.  geom = NULL is
 // gm_table_scan, launch for launch; with geom the survivors of the envelope pass are compacted as
-// candidate indices, refined against their geometries (geom_refine) and the mask is compacted again.
+// candidate indices, refined against their geometries (geom_refine; poly_refine when the filter carries
+// query polygons, whose parts' envelopes then stand in for the boxes) and the mask is compacted again.
 static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
                       const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
                       const gm_geom_column* geom, const int64_t* perm, int64_t* ids, int64_t ids_cap,
@@ -722,6 +723,20 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
   if (!f) f = &none;
   if (f->z3filter && f->z2filter) return set_error(who + ": a Z3Filter and a Z2Filter together"), GM_E_INVALID;
   if (f->z3filter && !bin) return set_error(who + ": a Z3Filter needs the bin column"), GM_E_INVALID;
+  // query polygons: the prefilter's boxes are the parts' envelopes, derived here
+  polyq::HostQuery hq;
+  gm_scan_filter with_boxes;
+  const bool polys = f->polys != nullptr;
+  if (polys) {
+    if (!geom) return set_error(who + ": polys needs the geometry column (gm_table_scan_geom)"), GM_E_INVALID;
+    if (f->boxes || f->n_boxes != 0) return set_error(who + ": polys and boxes together"), GM_E_INVALID;
+    if (const char* bad = polyq::validate(f->polys)) return set_error(who + ": " + bad), GM_E_INVALID;
+    polyq::build(f->polys, hq);
+    with_boxes = *f;
+    with_boxes.boxes = hq.penv.data();
+    with_boxes.n_boxes = hq.n_parts;
+    f = &with_boxes;
+  }
   const bool env = f->n_boxes > 0, dur = f->during != 0;
   if (f->n_boxes < 0 || (env && (!f->boxes || !f->xmin || !f->ymin || !f->xmax || !f->ymax)) || (dur && !f->t_ms))
     return GM_E_INVALID;
@@ -825,7 +840,14 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
         GM_CHECK_LAUNCH();
         const GeomRefine gr{surv, ne, coff, start, nr, total, ff.rows, f->xmin, f->ymin, f->xmax, f->ymax, ff.boxes,
                             f->n_boxes, b.mask, b.counts};
-        if ((rc = geom_refine(ctx, geom, gr))) return rc;
+        if (polys) {
+          PolyQuery pq;
+          if ((rc = upload_polys(ctx, tmp, hq, pq))) return rc;
+          rc = poly_refine(ctx, geom, gr, pq);
+        } else {
+          rc = geom_refine(ctx, geom, gr);
+        }
+        if (rc) return rc;
       }
     }
     rc = (geom && ne == 0) ? GM_OK : finish_scan(ctx, total, b, ids, ids_cap, &nm);
@@ -858,8 +880,9 @@ int gm_table_scan_geom(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, co
                        int64_t* n_match, int64_t* n_scanned, int64_t* n_envelope) {
   if (!ctx) return GM_E_INVALID;
   if (!f) return set_error("gm_table_scan_geom: the filter (query boxes, envelope columns) is required"), GM_E_INVALID;
-  if (f->n_boxes <= 0) return set_error("gm_table_scan_geom: at least one query box is required"), GM_E_INVALID;
-  if (!f->boxes || !f->xmin || !f->ymin || !f->xmax || !f->ymax)
+  if (!f->polys && f->n_boxes <= 0)
+    return set_error("gm_table_scan_geom: at least one query box is required"), GM_E_INVALID;
+  if ((!f->polys && !f->boxes) || !f->xmin || !f->ymin || !f->xmax || !f->ymax)
     return set_error("gm_table_scan_geom: the boxes and the four envelope columns are required"), GM_E_INVALID;
   if (!geom) return set_error("gm_table_scan_geom: the geometry column is required"), GM_E_INVALID;
   if (geom->ordinal_bits != 64 && geom->ordinal_bits != 32)

@@ -1,4 +1,5 @@
-// gm_geom_filter.hip -- the XZ tables' full filter on the feature GEOMETRY: geometry meets query box.
+// gm_geom_filter.hip -- the XZ tables' full filter on the feature GEOMETRY: geometry meets query box
+// (k_geom_refine, below) and geometry meets query polygons (k_poly_refine, further down, with its own notes).
 //
 // The XZ key spaces always apply the full filter (XZ2IndexKeySpace.scala:122-125,
 // XZ3IndexKeySpace.scala:247-250); for bbox(geom, ...) it is GeoTools BBOXImpl on the feature's geometry
@@ -244,6 +245,354 @@ __global__ __launch_bounds__(GTPB) void k_geom_refine(ArrowGeom g, GeomRefine a)
   }
 }
 
+// ------------------------------------------------------------------ geometry meets query polygons
+// k_poly_refine: INTERSECTS(geom, polygons), the contract of geomesa_hip.h.  Still one wave per envelope
+// survivor.  The query (PolyQuery, gm_scan.hpp) is its ring edges bucketed by y-slab; while the entries fit
+// PQ_LDS_ENTRIES they are staged in LDS once per workgroup, else read from global memory (L2).  Per tuple
+// run of G (a line, or a ring) the pair space is G's segments x the query's entries, in one of two shapes:
+//   * run_meets_a, 64 tuples or more: lanes stride over G's segments (line_meets' read pattern) and each
+//     lane loops the entries of the slabs its own segment's y-range overlaps;
+//   * run_meets_b, fewer segments than a wave: the run sits in registers, one tuple per lane; lanes stride
+//     over the entries of the slabs the SLOT's y-range overlaps (one contiguous run) and loop G's
+//     segments, each taken from its lanes by readlane.
+// A ring's pass also counts, for up to PQ_GROUP parts at once, the crossings of the part's first shell
+// vertex (RayCrossingCounter.countSegment) -- "Q's part inside G" -- as the box kernel counts its corner's.
+// Parts past the first PQ_GROUP take further passes over the rings, contact off, and only after contact
+// failed.  Without contact a line, or a polygon's shell, lies wholly inside or outside each part, and its
+// first tuple decides (pq_locate: the tuple's one slab, ring by ring, parts by the shell / hole rule).
+constexpr int PQ_LDS_ENTRIES = 2040;   // just under 64 KiB of entries per workgroup (the WKB stack follows them)
+constexpr int PQ_GROUP = 4;
+constexpr int PQ_MAX_BLOCKS = 1024;    // a staging workgroup strides over the survivors: 4 per CU
+
+extern __shared__ __attribute__((aligned(16))) char pq_smem[];
+
+template <bool LDS>
+struct QEdges {
+  const double* g;
+  __device__ __forceinline__ void get(int32_t e, double& ax, double& ay, double& bx, double& by) const {
+    const dv2* s = (LDS ? (const dv2*)pq_smem : (const dv2*)g) + 2 * (int64_t)e;
+    const dv2 a = s[0], b = s[1];
+    ax = a.x; ay = a.y; bx = b.x; by = b.y;
+  }
+};
+
+__device__ __forceinline__ int pq_slab(double y, const PolyQuery& q) {   // polyq::slab_of
+  const double c = floor(__dmul_rn(__dsub_rn(y, q.y0), q.inv_h));
+  return (int)__builtin_fmin(__builtin_fmax(c, 0.0), (double)(q.ns - 1));
+}
+
+// RobustLineIntersector.computeIntersect(p1, p2, q1, q2).hasIntersection()
+__device__ __forceinline__ bool seg_meets_seg(double ax, double ay, double bx, double by, double cx, double cy,
+                                              double dx, double dy) {
+  if ((ax < bx ? ax : bx) > (cx > dx ? cx : dx) || (ax > bx ? ax : bx) < (cx < dx ? cx : dx) ||
+      (ay < by ? ay : by) > (cy > dy ? cy : dy) || (ay > by ? ay : by) < (cy < dy ? cy : dy))
+    return false;
+  const int pq1 = jts_orientation(ax, ay, bx, by, cx, cy);
+  const int pq2 = jts_orientation(ax, ay, bx, by, dx, dy);
+  if ((pq1 > 0 && pq2 > 0) || (pq1 < 0 && pq2 < 0)) return false;
+  const int qp1 = jts_orientation(cx, cy, dx, dy, ax, ay);
+  const int qp2 = jts_orientation(cx, cy, dx, dy, bx, by);
+  if ((qp1 > 0 && qp2 > 0) || (qp1 < 0 && qp2 < 0)) return false;
+  if ((pq1 | pq2 | qp1 | qp2) == 0)   // computeCollinearIntersection
+    return pt_in_seg_env(ax, ay, bx, by, cx, cy) || pt_in_seg_env(ax, ay, bx, by, dx, dy) ||
+           pt_in_seg_env(cx, cy, dx, dy, ax, ay) || pt_in_seg_env(cx, cy, dx, dy, bx, by);
+  return true;
+}
+
+// one survivor's view of the query: the slot's envelope, the entries of the slabs it overlaps, and the
+// group of parts whose first shell vertex this walk counts (act: those inside the slot's envelope)
+template <bool LDS>
+struct PolyCtx {
+  PolyQuery q;
+  QEdges<LDS> ed;
+  int lane;
+  int32_t be0, be1;
+  bool contact;            // this walk tests contact and locates first tuples (the first group's)
+  int p0;                  // the group's first part
+  uint32_t act;
+  double vx[PQ_GROUP], vy[PQ_GROUP];
+};
+
+// the point is not exterior to some part.  Every lane for itself: the entries of the point's slab in
+// order, a ring's crossings closed when the ring changes and a part's rule when the part does
+template <bool LDS>
+__device__ __forceinline__ bool pq_locate(const PolyCtx<LDS>& c, double px, double py) {
+  const PolyQuery& q = c.q;
+  if (!(px >= q.x0 && px <= q.x1 && py >= q.y0 && py <= q.y1)) return false;
+  const int s = pq_slab(py, q);
+  const int32_t e1 = q.soff[s + 1];
+  bool hit = false, shell_ok = false, hole_in = false, shell = false, on = false;
+  int32_t cur_r = -1, cur_p = -1;
+  int cr = 0;
+  for (int32_t e = q.soff[s]; e < e1; ++e) {
+    const int32_t r = q.ering[e], pw = q.epart[e];
+    if (r != cur_r) {
+      if (cur_r >= 0) {
+        if (shell) shell_ok = on || (cr & 1); else hole_in |= !on && (cr & 1);
+      }
+      if ((pw >> 1) != cur_p) {
+        hit |= shell_ok && !hole_in;
+        cur_p = pw >> 1;
+        shell_ok = hole_in = false;
+      }
+      cur_r = r;
+      shell = pw & 1;
+      cr = 0;
+      on = false;
+    }
+    if (!on) {
+      double ax, ay, bx, by;
+      c.ed.get(e, ax, ay, bx, by);
+      on = count_segment(ax, ay, bx, by, px, py, cr);
+    }
+  }
+  if (cur_r >= 0) {
+    if (shell) shell_ok = on || (cr & 1); else hole_in |= !on && (cr & 1);
+  }
+  return hit || (shell_ok && !hole_in);
+}
+
+// a lane's segment against the entries of the slabs its y-range overlaps
+template <bool LDS>
+__device__ __forceinline__ bool seg_meets_query(const PolyCtx<LDS>& c, double ax, double ay, double bx, double by) {
+  const PolyQuery& q = c.q;
+  const double sy0 = ay < by ? ay : by, sy1 = ay > by ? ay : by;
+  if (sy1 < q.y0 || sy0 > q.y1 || (ax > bx ? ax : bx) < q.x0 || (ax < bx ? ax : bx) > q.x1) return false;
+  const int32_t e1 = q.soff[pq_slab(sy1, q) + 1];
+  for (int32_t e = q.soff[pq_slab(sy0, q)]; e < e1; ++e) {
+    double cx, cy, dx, dy;
+    c.ed.get(e, cx, cy, dx, dy);
+    if (seg_meets_seg(ax, ay, bx, by, cx, cy, dx, dy)) return true;
+  }
+  return false;
+}
+
+// the first-vertex crossings of the group's active parts over one segment of a ring of G; true: on it
+template <bool LDS>
+__device__ __forceinline__ bool count_group(const PolyCtx<LDS>& c, double ax, double ay, double bx, double by,
+                                            int (&cross)[PQ_GROUP]) {
+  bool on = false;
+#pragma unroll
+  for (int k = 0; k < PQ_GROUP; ++k)
+    if ((c.act >> k) & 1u) on |= count_segment(ax, ay, bx, by, c.vx[k], c.vy[k], cross[k]);
+  return on;
+}
+
+// the tuples [a, b), b - a >= 2, as a line or a ring: some segment meets a query edge (when c.contact); a
+// RING also gives the parities of the group's crossings in par (true as well when a first vertex is on it)
+template <bool RING, bool LDS, class SRC>
+__device__ __forceinline__ bool run_meets_a(const SRC& g, int32_t a, int32_t b, const PolyCtx<LDS>& c, uint32_t& par) {
+  int cross[PQ_GROUP] = {0, 0, 0, 0};
+  for (int32_t j0 = a; j0 < b - 1; j0 += 63) {
+    const int32_t j = j0 + c.lane;
+    double ax = 0.0, ay = 0.0;
+    if (j < b) g.tuple(j, ax, ay);
+    const double bx = __shfl_down(ax, 1, 64), by = __shfl_down(ay, 1, 64);
+    bool h = false;
+    if (c.lane < 63 && j < b - 1) {
+      if (c.contact) h = seg_meets_query(c, ax, ay, bx, by);
+      if (RING && !h) h = count_group(c, ax, ay, bx, by, cross);
+    }
+    if (__any(h)) return true;
+  }
+  par = 0;
+  if (RING) {
+#pragma unroll
+    for (int k = 0; k < PQ_GROUP; ++k) par |= (uint32_t)(__popcll(__ballot(cross[k] & 1)) & 1) << k;
+  }
+  return false;
+}
+
+__device__ __forceinline__ double lane_of(double v, int k) {   // v of lane k, k wave-uniform
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), k), hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
+  return __hiloint2double(hi, lo);
+}
+
+// the same for 2 <= b - a <= 64: the run in registers, lanes over the query's entries.  Lane k < PQ_GROUP
+// counts part k's first vertex, once, in the first step over the entries
+template <bool RING, bool LDS, class SRC>
+__device__ __forceinline__ bool run_meets_b(const SRC& g, int32_t a, int32_t b, const PolyCtx<LDS>& c, uint32_t& par) {
+  double tx = 0.0, ty = 0.0;
+  if (a + c.lane < b) g.tuple(a + c.lane, tx, ty);
+  const int nseg = b - a - 1;
+  const bool counts = RING && c.lane < PQ_GROUP && ((c.act >> c.lane) & 1u);
+  double vx = 0.0, vy = 0.0;
+  if (counts) {   // an active part's: from memory, since a lane-indexed c.vx[] would put c into scratch
+    vx = c.q.pv0[2 * (c.p0 + c.lane)];
+    vy = c.q.pv0[2 * (c.p0 + c.lane) + 1];
+  }
+  int cross = 0;
+  int32_t e0 = c.contact ? c.be0 : c.be1;
+  bool first = true;
+  do {
+    const int32_t e = e0 + c.lane;
+    const bool have = e < c.be1;
+    double cx = 0.0, cy = 0.0, dx = 0.0, dy = 0.0;
+    if (have) c.ed.get(e, cx, cy, dx, dy);
+    bool h = false;
+    for (int k = 0; k < nseg; ++k) {
+      const double ax = lane_of(tx, k), ay = lane_of(ty, k), bx = lane_of(tx, k + 1), by = lane_of(ty, k + 1);
+      if (have && !h) h = seg_meets_seg(ax, ay, bx, by, cx, cy, dx, dy);
+      if (counts && first && !h) h = count_segment(ax, ay, bx, by, vx, vy, cross);
+    }
+    if (__any(h)) return true;
+    first = false;
+    e0 += 64;
+  } while (e0 < c.be1);
+  par = RING ? (uint32_t)__ballot(cross & 1) & ((1u << PQ_GROUP) - 1u) : 0u;
+  return false;
+}
+
+template <bool RING, bool LDS, class SRC>
+__device__ __forceinline__ bool run_meets(const SRC& g, int32_t a, int32_t b, const PolyCtx<LDS>& c, uint32_t& par) {
+  return b - a <= 64 ? run_meets_b<RING>(g, a, b, c, par) : run_meets_a<RING>(g, a, b, c, par);
+}
+
+template <bool LDS, class SRC>
+__device__ __forceinline__ bool first_tuple_in(const SRC& g, int64_t a, const PolyCtx<LDS>& c) {
+  double x, y;
+  g.tuple(a, x, y);
+  return pq_locate(c, x, y);
+}
+
+// a line: contact, else its first tuple (one tuple: that point)
+template <bool LDS, class SRC>
+__device__ __forceinline__ bool line_meets_polys(const SRC& g, int32_t a, int32_t b, const PolyCtx<LDS>& c) {
+  if (!c.contact || b <= a) return false;
+  uint32_t unused;
+  if (b - a >= 2 && run_meets<false>(g, a, b, c, unused)) return true;
+  return first_tuple_in(g, a, c);
+}
+
+// one ring of a polygon of G: contact; the shell's first tuple; the group's parities into in_shell / in_hole
+template <bool LDS, class SRC>
+__device__ __forceinline__ bool ring_meets_polys(const SRC& g, int32_t a, int32_t b, bool is_shell, const PolyCtx<LDS>& c,
+                                 uint32_t& in_shell, uint32_t& in_hole) {
+  if (b <= a) return false;
+  uint32_t par = 0;
+  if (b - a >= 2 && (c.contact || c.act) && run_meets<true>(g, a, b, c, par)) return true;
+  if (is_shell) in_shell = par; else in_hole |= par;
+  return is_shell && c.contact && first_tuple_in(g, a, c);
+}
+
+template <bool LDS, class SRC>
+__device__ __forceinline__ bool polygon_meets_polys(const SRC& g, const int32_t* __restrict__ ro, int32_t r0, int32_t r1,
+                                    const PolyCtx<LDS>& c) {
+  uint32_t in_shell = 0, in_hole = 0;
+  for (int32_t r = r0; r < r1; ++r)
+    if (ring_meets_polys(g, uoff(ro, r), uoff(ro, r + 1), r == r0, c, in_shell, in_hole)) return true;
+  return (in_shell & ~in_hole & c.act) != 0;
+}
+
+template <bool LDS, class SRC>
+__device__ __forceinline__ bool points_meet_polys(const SRC& g, int32_t a, int32_t b, const PolyCtx<LDS>& c) {
+  if (!c.contact) return false;
+  for (int32_t j0 = a; j0 < b; j0 += 64) {
+    const int32_t j = j0 + c.lane;
+    bool h = false;
+    if (j < b) h = first_tuple_in(g, j, c);
+    if (__any(h)) return true;
+  }
+  return false;
+}
+
+// slot i meets a part (wave-uniform), for the group of parts c holds
+template <bool F32, bool LDS>
+__device__ __forceinline__ bool geom_meets_polys(const ArrowGeom& g, int64_t i, const PolyCtx<LDS>& c) {
+  const ArrowTuples<F32> ts = tuples_of<F32>(g);
+  switch (g.type) {
+    case GM_GEOM_POINT:
+      return c.contact && first_tuple_in(ts, i, c);
+    case GM_GEOM_MULTIPOINT:
+      return points_meet_polys(ts, uoff(g.o0, i), uoff(g.o0, i + 1), c);
+    case GM_GEOM_LINESTRING:
+      return line_meets_polys(ts, uoff(g.o0, i), uoff(g.o0, i + 1), c);
+    case GM_GEOM_POLYGON:
+      return polygon_meets_polys(ts, g.o1, uoff(g.o0, i), uoff(g.o0, i + 1), c);
+    case GM_GEOM_MULTILINESTRING: {
+      const int32_t l1 = uoff(g.o0, i + 1);
+      for (int32_t l = uoff(g.o0, i); l < l1; ++l)
+        if (line_meets_polys(ts, uoff(g.o1, l), uoff(g.o1, l + 1), c)) return true;
+      return false;
+    }
+    default: {   // GM_GEOM_MULTIPOLYGON
+      const int32_t p1 = uoff(g.o0, i + 1);
+      for (int32_t p = uoff(g.o0, i); p < p1; ++p)
+        if (polygon_meets_polys(ts, g.o2, uoff(g.o1, p), uoff(g.o1, p + 1), c)) return true;
+      return false;
+    }
+  }
+}
+
+// the visitor of a WKB slot, beside WkbMeets: each class decided as geom_meets_polys decides it
+template <bool LDS>
+struct WkbMeetsPolys {
+  const PolyCtx<LDS>& c;
+  uint32_t in_shell, in_hole;
+  __device__ __forceinline__ bool point(const WkbTuples& t) { return c.contact && first_tuple_in(t, 0, c); }
+  __device__ __forceinline__ bool line(const WkbTuples& t, uint32_t n) { return line_meets_polys(t, 0, (int32_t)n, c); }
+  __device__ __forceinline__ void polygon_begin() { in_shell = in_hole = 0; }
+  __device__ __forceinline__ bool ring(uint32_t r, const WkbTuples& t, uint32_t n) {
+    return ring_meets_polys(t, 0, (int32_t)n, r == 0, c, in_shell, in_hole);
+  }
+  __device__ __forceinline__ bool polygon_end() { return (in_shell & ~in_hole & c.act) != 0; }
+};
+
+template <bool F32, bool WKB, bool LDS>
+__global__ __launch_bounds__(GTPB) void k_poly_refine(ArrowGeom g, GeomRefine a, PolyQuery q) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t nwaves = (int64_t)gridDim.x * (GTPB / 64);
+  if (LDS) {
+    for (int32_t i = threadIdx.x; i < 2 * q.entries; i += GTPB) ((dv2*)pq_smem)[i] = ((const dv2*)q.edge)[i];
+    __syncthreads();
+  }
+  // wkb_walk's stack, one column per wave, behind the staged entries
+  uint32_t* s_rem = (uint32_t*)(pq_smem + (LDS ? (size_t)q.entries * 32 : 0));
+  const bool areal = WKB || g.type == GM_GEOM_POLYGON || g.type == GM_GEOM_MULTIPOLYGON;
+  PolyCtx<LDS> c;
+  c.q = q;
+  c.ed = QEdges<LDS>{q.edge};
+  c.lane = lane;
+  for (int64_t s = (int64_t)blockIdx.x * (GTPB / 64) + wave; s < a.n_surv; s += nwaves) {
+    const int64_t cand = a.surv[s];
+    const int64_t row = cand_row(a.coff, a.start, a.nr, cand);
+    const int64_t r = a.rows ? a.rows[row] : row;
+    bool hit = false;
+    if (arrow_valid(g.valid, g.voff, r)) {
+      const double ex0 = a.xmin[r], ey0 = a.ymin[r], ex1 = a.xmax[r], ey1 = a.ymax[r];
+      // a null envelope (an empty or malformed slot) overlaps no slab and holds no first vertex
+      const bool any = ex1 >= ex0 && !(ey1 < q.y0 || ey0 > q.y1 || ex1 < q.x0 || ex0 > q.x1);
+      c.be0 = any ? q.soff[pq_slab(ey0, q)] : 0;
+      c.be1 = any ? q.soff[pq_slab(ey1, q) + 1] : 0;
+      const int groups = any ? (areal ? (q.n_parts + PQ_GROUP - 1) / PQ_GROUP : 1) : 0;
+      for (int gi = 0; gi < groups && !hit; ++gi) {
+        c.contact = gi == 0;
+        c.p0 = gi * PQ_GROUP;
+        c.act = 0;
+#pragma unroll
+        for (int k = 0; k < PQ_GROUP; ++k) {
+          const int p = gi * PQ_GROUP + k;
+          c.vx[k] = c.vy[k] = 0.0;
+          if (areal && p < q.n_parts) {
+            c.vx[k] = q.pv0[2 * p];
+            c.vy[k] = q.pv0[2 * p + 1];
+            if (c.vx[k] >= ex0 && c.vx[k] <= ex1 && c.vy[k] >= ey0 && c.vy[k] <= ey1) c.act |= 1u << k;
+          }
+        }
+        if (!c.contact && !c.act) continue;
+        if (WKB) {
+          WkbMeetsPolys<LDS> v{c, 0, 0};
+          hit = wkb_walk<true>(wkb_slot(g, r), s_rem + wave, GTPB / 64, v) == WKB_STOP;
+        } else {
+          hit = geom_meets_polys<F32>(g, r, c);
+        }
+      }
+    }
+    if (!hit && lane == 0) atomicAnd((unsigned long long*)&a.mask[cand >> 6], ~(1ull << (cand & 63)));
+  }
+}
+
 // per-block match counts of a candidate mask (the block_counts of pass A), one wave per block
 __global__ __launch_bounds__(64) void k_mask_recount(const uint64_t* __restrict__ mask, int64_t total,
                                                      int32_t* __restrict__ counts) {
@@ -301,6 +650,41 @@ int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a) {
       hipLaunchKernelGGL((k_geom_refine<F(), false>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, a);
     }, geom->ordinal_bits == 32);
   }
+  GM_CHECK_LAUNCH();
+  const int64_t nblocks = (a.total + FROWS - 1) / FROWS;
+  hipLaunchKernelGGL(k_mask_recount, dim3((unsigned)nblocks), dim3(64), 0, ctx->stream, a.mask, a.total, a.counts);
+  GM_CHECK_LAUNCH();
+  return GM_OK;
+}
+
+int upload_polys(gm_ctx* ctx, DevTemps& tmp, const polyq::HostQuery& h, PolyQuery& q) {
+  // [entries x 4 f64][parts x 2 f64][slab offsets][entry rings][entry parts]
+  const size_t nb = (size_t)h.entries(), np = (size_t)h.n_parts, no = h.soff.size();
+  std::vector<double> buf(nb * 4 + np * 2 + (no + 2 * nb + 1) / 2);
+  int32_t* words = (int32_t*)(buf.data() + nb * 4 + np * 2);
+  std::copy(h.edge.begin(), h.edge.end(), buf.begin());
+  std::copy(h.pv0.begin(), h.pv0.end(), buf.begin() + nb * 4);
+  std::copy(h.soff.begin(), h.soff.end(), words);
+  std::copy(h.ering.begin(), h.ering.end(), words + no);
+  std::copy(h.epart.begin(), h.epart.end(), words + no + nb);
+  double* d = nullptr;
+  int rc = tmp.alloc_async(buf.size() * 8, &d);
+  if (!rc) rc = copy_h2d(ctx, d, buf.data(), buf.size() * 8);
+  if (rc) return rc;
+  const int32_t* dw = (const int32_t*)(d + nb * 4 + np * 2);
+  q = PolyQuery{d, dw + no, dw + no + nb, dw, d + nb * 4, h.n_parts, h.ns, (int32_t)nb, h.x0, h.y0, h.x1, h.y1, h.inv_h};
+  return GM_OK;
+}
+
+int poly_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a, const PolyQuery& q) {
+  const ArrowGeom g = to_geom(geom);
+  const bool lds = q.entries <= PQ_LDS_ENTRIES, wkb = geom->type == GM_GEOM_WKB;
+  const int64_t blocks = std::min<int64_t>((a.n_surv + GTPB / 64 - 1) / (GTPB / 64), lds ? PQ_MAX_BLOCKS : 1 << 20);
+  const size_t smem = (lds ? (size_t)q.entries * 32 : 0) + (wkb ? WKB_DEPTH * (GTPB / 64) * sizeof(uint32_t) : 0);
+  with_flags([&](auto F, auto W, auto L) {
+    if constexpr (!(F() && W()))   // a WKB column holds doubles
+      hipLaunchKernelGGL((k_poly_refine<F(), W(), L()>), dim3((unsigned)blocks), dim3(GTPB), smem, ctx->stream, g, a, q);
+  }, geom->ordinal_bits == 32 && !wkb, wkb, lds);
   GM_CHECK_LAUNCH();
   const int64_t nblocks = (a.total + FROWS - 1) / FROWS;
   hipLaunchKernelGGL(k_mask_recount, dim3((unsigned)nblocks), dim3(64), 0, ctx->stream, a.mask, a.total, a.counts);

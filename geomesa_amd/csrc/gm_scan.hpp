@@ -6,6 +6,7 @@
 #pragma once
 
 #include "gm_internal.hpp"
+#include "gm_poly_query_host.hpp"
 
 namespace gm {
 
@@ -337,5 +338,21 @@ struct GeomRefine {
   int32_t* counts;
 };
 int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a);
+
+// The query polygons of gm_scan_filter.polys on the device (gm_poly_query_host.hpp builds them): the ring
+// edges bucketed by y-slab, each entry with its coordinates, its ring and its part * 2 + shell flag, and
+// each part's first shell vertex.  The parts' envelopes are the boxes of the mask pass.
+struct PolyQuery {
+  const double* edge;              // entries x (ax, ay, bx, by), slab by slab, ring order within a slab
+  const int32_t *ering, *epart;
+  const int32_t* soff;             // ns + 1
+  const double* pv0;               // n_parts x (x, y)
+  int32_t n_parts, ns, entries;
+  double x0, y0, x1, y1, inv_h;    // the envelope of every ring; slabs per unit of y
+};
+// the host images into `tmp`, one copy (synchronises the stream)
+int upload_polys(gm_ctx* ctx, DevTemps& tmp, const polyq::HostQuery& h, PolyQuery& q);
+// geom_refine against the query polygons: candidate surv[s] keeps its bit iff its slot meets a part
+int poly_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a, const PolyQuery& q);
 
 }  // namespace gm

@@ -305,8 +305,8 @@ class _KeyTable:
     def table_scan(self, arr, flt=None, map_rows=True, ids_cap=None, geom=None):
         """gm_table_scan over gm_key_range rows `arr` with a ScanFilter (None = no filter): (ids, n_match,
         n_scanned); ids are input rows (map_rows) or table rows.  With geom (a GeometryColumn in the order
-        of flt's envelope columns) the full filter is exact, geometry against box (gm_table_scan_geom), and
-        self.n_envelope keeps the number of candidates the envelope test let through."""
+        of flt's envelope columns) the full filter is exact, geometry against flt's boxes or its polys
+        (gm_table_scan_geom), and self.n_envelope keeps the number of candidates the envelope test let through."""
         import torch
         arr = np.ascontiguousarray(arr, _lib.KEY_RANGE_DTYPE)
         cap = self.n if ids_cap is None else ids_cap
@@ -334,6 +334,17 @@ class _KeyTable:
             raise IllegalArgumentException("exact=True needs a table that holds geometries (from_geometries)")
         return self.geom if exact else None
 
+    def _polygon_query(self, bboxes, polygons, exact):
+        """query()'s polygons argument checked: (PolygonSet, the parts' envelopes for range planning)."""
+        from .curve import IllegalArgumentException
+        if bboxes is not None:
+            raise IllegalArgumentException("give bboxes or polygons, not both")
+        if self.geom is None:
+            raise IllegalArgumentException("polygons needs a table that holds geometries (from_geometries)")
+        if exact is not None and not exact:
+            raise IllegalArgumentException("polygons are answered on the geometries: exact=False is not available")
+        return _query_polygons(polygons)
+
 
 def _geometry_envelopes(geoms, kind, flip_axis):
     """from_geometries' first steps: the GeometryColumn, its envelope columns, and the envelopes the keys
@@ -349,15 +360,43 @@ def _geometry_envelopes(geoms, kind, flip_axis):
     return col, env, tuple(torch.where(null, zero, c) for c in env)
 
 
-def _full_filter(cols, boxes, interval=None, t=None, perm=None):
+def _query_polygons(polygons):
+    """query()'s polygons argument -> (join.PolygonSet, its parts' envelopes: the shells', as boxes)."""
+    from .curve import IllegalArgumentException
+    from .join import PolygonSet
+    ps = polygons
+    if not isinstance(ps, PolygonSet):
+        polygons = list(polygons)
+        ps = (PolygonSet.from_wkt(polygons) if polygons and all(isinstance(p, str) for p in polygons)
+              else PolygonSet.from_polygons(polygons))
+    n_parts = int(ps.poly_part_off[-1]) if len(ps.poly_part_off) else 0
+    if n_parts == 0:
+        raise IllegalArgumentException("polygons: at least one polygon part is needed")
+    boxes = []
+    for p in range(n_parts):
+        r = int(ps.part_ring_off[p])
+        a, b = int(ps.ring_vert_off[r]), int(ps.ring_vert_off[r + 1])
+        if b <= a:
+            raise IllegalArgumentException("polygons: a part with an empty shell")
+        x, y = ps.vx[a:b], ps.vy[a:b]
+        boxes.append((float(x.min()), float(y.min()), float(x.max()), float(y.max())))
+    return ps, boxes
+
+
+def _full_filter(cols, boxes, interval=None, t=None, perm=None, polys=None):
     """ScanFilter for the XZ full filter: envelope columns x boxes, dtg during (lo, hi) exclusive.  cols
     and t are in input order and perm (the table's) takes a table row to them, whatever the scan maps its
-    ids through.  The host arrays the filter points to are returned beside it (they must outlive the
-    call)."""
+    ids through.  polys (a join.PolygonSet) takes the place of the boxes: INTERSECTS against the polygons,
+    gm_table_scan_geom only.  The host arrays the filter points to are returned beside it (they must
+    outlive the call)."""
     f = _lib.ScanFilter()
     keep = []
     if perm is not None:
         f.rows = perm.data_ptr()
+    if polys is not None:
+        keep += [polys, polys.c_struct()]
+        f.xmin, f.ymin, f.xmax, f.ymax = (c.data_ptr() for c in cols)
+        f.polys, boxes = ctypes.addressof(keep[-1]), None
     if boxes:
         bx = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
         keep.append(bx)
@@ -419,16 +458,22 @@ class XZ2Table(_KeyTable):
         tb.env, tb.geom = env, col
         return tb
 
-    def query(self, bboxes=None, target=2000, full_filter=True, exact=None):
+    def query(self, bboxes=None, target=2000, full_filter=True, exact=None, polygons=None):
         """exact: the full filter on the geometries (BBOX itself) rather than on their envelopes; None =
-        exact when the table holds geometries."""
+        exact when the table holds geometries.  polygons (a join.PolygonSet, or what its from_polygons /
+        from_wkt take) instead of bboxes: INTERSECTS(geom, polygon) on the geometries, the ranges planned
+        from the parts' envelopes."""
+        ps = None
+        if polygons is not None:
+            ps, bboxes = self._polygon_query(bboxes, polygons, exact)
         geom = self._exact_geom(exact)
         v = self.ks.get_index_values(bboxes)
         if v.disjoint:
             import torch
             return torch.zeros(0, dtype=torch.int64, device=self.z.device), 0, 0
         arr, _ = key_ranges(self.ks.get_ranges(v, target=target), self.shards)
-        f, keep = _full_filter(self.env, v.spatialBounds, perm=self.perm) if full_filter else (None, [])
+        f, keep = (_full_filter(self.env, v.spatialBounds, perm=self.perm, polys=ps) if full_filter
+                   else (None, []))
         return self.table_scan(arr, f, geom=geom if full_filter else None)
 
 
@@ -464,14 +509,19 @@ class XZ3Table(_KeyTable):
         tb.env, tb.geom = env, col
         return tb
 
-    def query(self, bboxes=None, interval=None, target=2000, full_filter=True, exact=None):
-        """interval: (lo, hi) epoch millis of `dtg DURING lo/hi`, or None.  exact: as XZ2Table.query."""
+    def query(self, bboxes=None, interval=None, target=2000, full_filter=True, exact=None, polygons=None):
+        """interval: (lo, hi) epoch millis of `dtg DURING lo/hi`, or None.  exact and polygons: as
+        XZ2Table.query."""
         from .keyspace import during
+        ps = None
+        if polygons is not None:
+            ps, bboxes = self._polygon_query(bboxes, polygons, exact)
         geom = self._exact_geom(exact)
         v = self.ks.get_index_values(bboxes, [during(*interval)] if interval is not None else None)
         if v.disjoint:
             import torch
             return torch.zeros(0, dtype=torch.int64, device=self.z.device), 0, 0
         arr, _ = key_ranges(self.ks.get_ranges(v, target=target), self.shards)
-        f, keep = _full_filter(self.env, v.spatialBounds, interval, self.t, self.perm) if full_filter else (None, [])
+        f, keep = (_full_filter(self.env, v.spatialBounds, interval, self.t, self.perm, polys=ps) if full_filter
+                   else (None, []))
         return self.table_scan(arr, f, geom=geom if full_filter else None)

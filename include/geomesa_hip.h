@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 1
+/* 2: gm_scan_filter gained its last member, polys.  A shim compiled against version 1 passes a shorter
+   struct and must be rebuilt. */
+#define GM_ABI_VERSION 2
 
 /* return codes */
 #define GM_OK 0
@@ -623,7 +625,10 @@ int gm_key_range_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
    - rows (device, optional): the column row of each table row, i.e. where table row r's envelope and
      dtg are found (xmin[rows[r]], ...).  NULL: gm_table_scan's perm argument maps them (columns in
      INPUT order); both NULL: the columns are in table order.  rows only reaches the full filter's
-     columns; the ids that come back are mapped by perm alone. */
+     columns; the ids that come back are mapped by perm alone;
+   - polys (host, optional; gm_table_scan_geom only): the query geometry as polygons instead of boxes, see
+     gm_table_scan_geom.  NULL: boxes, as before the member existed.  With polys, boxes must be NULL and
+     n_boxes 0; gm_table_scan refuses a filter with polys (GM_E_INVALID). */
 typedef struct {
   const uint8_t* z3filter;
   size_t z3filter_len;
@@ -640,7 +645,12 @@ typedef struct {
   int64_t t_lo;
   int64_t t_hi;
   const int64_t* rows;
+  const gm_polyset* polys;
 } gm_scan_filter;
+/* the most ring tuples (closing tuples included) a query polygon set may hold: its edges, bucketed by
+   y-slab with at most 2 entries per edge, go to the device once per call, 40 B per entry (5 MiB at the
+   cap) */
+#define GM_POLY_QUERY_MAX_VERTICES 65536
 /* Seek-and-filter over any sorted key table (gm_sort_keys order): Z3 and XZ3 tables ([shard][bin][z]),
    Z2 and XZ2 tables (bin = NULL: [shard][z]).  Every row inside any of the ranges (host array, merged as
    gm_key_range_scan merges them; for bin = NULL give bin_lo = bin_hi = 0, XZ2IndexKeySpace.getRangeBytes
@@ -668,7 +678,30 @@ int gm_table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const i
    gm_table_scan's.
    A GM_GEOM_WKB slot (ordinal_bits 64, coords and offsets[0]) is decided per class in the same way: a
    collection matches iff any element does, a LineString of one tuple is that point, and a malformed slot
-   never matches -- its envelope column holds the null envelope, which is what keeps it from the walk. */
+   never matches -- its envelope column holds the null envelope, which is what keeps it from the walk.
+
+   INTERSECTS against query polygons: f->polys (host) in place of the boxes (f->boxes NULL, f->n_boxes 0,
+   else GM_E_INVALID).  Each polygon of the set has parts, each part a shell and holes, rings closed.  A part
+   is the closed set "inside or on the shell, and not strictly inside a hole"; slot G matches iff G and at
+   least one part share a point.  A null slot, an empty geometry and a malformed WKB slot never match, a
+   collection matches iff any element does, a LineString of one tuple is that point.  The decision:
+     1. the envelope prefilter, unchanged, with the JTS envelope of each part (of its shell) as the boxes,
+        derived here; *n_envelope reports its survivors;
+     2. contact: a segment of G meets a ring segment of a part (shell or hole), decided as
+        RobustLineIntersector.computeIntersect decides hasIntersection: the segments' envelopes overlap,
+        the orientation signs of one segment's ends about the other are not both positive or both negative,
+        either way round, and with all four zero an endpoint lies in the other segment's envelope;
+     3. containment, reached only without contact, when every connected piece of G (each point, line and
+        polygon shell) lies wholly inside or wholly outside each part: the first tuple of a piece is not
+        exterior to some part (RayCrossingCounter ring by ring; inside or on the shell and strictly inside
+        no hole -- not Mod-2 over the rings; for a point this is also where "on the boundary" is found), or,
+        for a polygon of G, the first shell vertex of some part is inside that polygon by the same rule over
+        its rings.
+   Every query ring is closed, has at least 4 tuples and finite ordinates, the set has at least one part and
+   at most GM_POLY_QUERY_MAX_VERTICES tuples, else GM_E_INVALID with a gm_last_error text -- never a
+   fallback.  A self-intersecting query polygon is answered by the procedure as written; its parity with
+   JTS is unpinned.  JTS 1.20 answers a non-rectangular intersects through RelateOp, which is not in the
+   reference tree: parity beyond this closed-set definition is unpinned. */
 int gm_table_scan_geom(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
                        const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
                        const gm_geom_column* geom, const int64_t* perm, int64_t* ids, int64_t ids_cap,
