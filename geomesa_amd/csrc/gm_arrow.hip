@@ -230,7 +230,7 @@ __global__ __launch_bounds__(ATPB) void k_points_soa_wkb(ArrowGeom g, int64_t n,
 }
 
 // ------------------------------------------------------------------ envelopes (XZ keys)
-// (Env, ArrowGeom and geom_envelope: gm_arrow.hpp)
+// (Env, ArrowGeom and EnvelopeOf: gm_arrow.hpp; slot_envelope: gm_wkb.hpp)
 
 // XZ2IndexKeySpace / XZ3IndexKeySpace.toIndexKey over an Arrow geometry column; DIM 3 also bins the date.
 // WKB: a GM_GEOM_WKB column (F32 false), a malformed slot keyed as a null one
@@ -244,12 +244,9 @@ __global__ __launch_bounds__(ATPB) void k_xz_key_arrow(ArrowGeom g, ArrowTime tc
     int16_t b = 0;
     uint8_t st;
     Env e;
-    bool valid = arrow_valid(g.valid, g.voff, i);
-    if (WKB) valid = valid && wkb_envelope(g, i, s_rem + threadIdx.x, ATPB, e);
-    if (!valid) {
+    if (!arrow_valid(g.valid, g.voff, i) || !slot_envelope<F32, WKB>(g, i, s_rem + threadIdx.x, ATPB, e)) {
       st = ST_NULL_GEOM;
     } else {
-      if (!WKB) e = geom_envelope<F32>(g, i);
       if (DIM == 2) {
         st = xz2_one<LENIENT>(gp, e.minx, e.miny, e.maxx, e.maxy, out);
       } else {

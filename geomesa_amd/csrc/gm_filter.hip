@@ -710,8 +710,8 @@ int gm_strict_scan(gm_ctx* ctx, const double* x, const double* y, const int64_t*
 
 // gm_table_scan and gm_table_scan_geom: the seek, the mask pass and the compaction.  geom = NULL is
 // gm_table_scan, launch for launch; with geom the survivors of the envelope pass are compacted as
-// candidate indices, refined against their geometries (geom_refine; poly_refine when the filter carries
-// query polygons, whose parts' envelopes then stand in for the boxes) and the mask is compacted again.
+// candidate indices, refined against their geometries (geom_refine; against the query polygons when the
+// filter carries them, whose parts' envelopes then stand in for the boxes) and the mask is compacted again.
 static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
                       const gm_key_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
                       const gm_geom_column* geom, const int64_t* perm, int64_t* ids, int64_t ids_cap,
@@ -840,14 +840,9 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
         GM_CHECK_LAUNCH();
         const GeomRefine gr{surv, ne, coff, start, nr, total, ff.rows, f->xmin, f->ymin, f->xmax, f->ymax, ff.boxes,
                             f->n_boxes, b.mask, b.counts};
-        if (polys) {
-          PolyQuery pq;
-          if ((rc = upload_polys(ctx, tmp, hq, pq))) return rc;
-          rc = poly_refine(ctx, geom, gr, pq);
-        } else {
-          rc = geom_refine(ctx, geom, gr);
-        }
-        if (rc) return rc;
+        PolyQuery pq;
+        if (polys && (rc = upload_polys(ctx, tmp, hq, pq))) return rc;
+        if ((rc = geom_refine(ctx, geom, gr, polys ? &pq : nullptr))) return rc;
       }
     }
     rc = (geom && ne == 0) ? GM_OK : finish_scan(ctx, total, b, ids, ids_cap, &nm);

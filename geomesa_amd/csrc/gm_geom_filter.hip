@@ -1,16 +1,19 @@
-// gm_geom_filter.hip -- the XZ tables' full filter on the feature GEOMETRY: geometry meets query box
-// (k_geom_refine, below) and geometry meets query polygons (k_poly_refine, further down, with its own notes).
+// gm_geom_filter.hip -- the XZ tables' full filter on the feature GEOMETRY: geometry meets query box (k_refine
+// with BoxPred and its visitor MeetsBox, below) and geometry meets query polygons (k_poly_refine, further
+// down, with its own notes).  In k_refine the kernel owns the survivors, a predicate owns the query, and a
+// visitor of the slot's walk (arrow_walk, gm_arrow.hpp; wkb_walk, gm_wkb.hpp) owns the decision per point,
+// line and ring, over typed and WKB columns alike.
 //
 // The XZ key spaces always apply the full filter (XZ2IndexKeySpace.scala:122-125,
 // XZ3IndexKeySpace.scala:247-250); for bbox(geom, ...) it is GeoTools BBOXImpl on the feature's geometry
 // (GeometryProcessing.scala:104-136), i.e. JTS Geometry.intersects against the query rectangle.  The
 // contract here is the closed-set one: slot G matches box B iff G and B share a point.  JTS 1.20
 // RectangleIntersects gets there by an envelope check, GeometryContainsPointVisitor over the
-// rectangle's corners and RectangleLineIntersector per segment; so does k_geom_refine:
+// rectangle's corners and RectangleLineIntersector per segment; so does the box predicate:
 //   * the envelope test is the mask pass of the scan (k_range_mask, gm_filter.hip); its survivors come
 //     here as compacted candidate indices, one 64-lane wave per survivor;
-//   * lanes stride over the slot's segments (consecutive tuples: one contiguous run per wave step, each
-//     tuple loaded once, a segment's second end taken from the next lane).
+//   * lanes stride over the slot's segments (segments_any: consecutive tuples, one contiguous run per wave
+//     step, each tuple loaded once, a segment's second end taken from the next lane).
 //     RectangleLineIntersector: segment envelope, an endpoint in the box, else the segment ordered by
 //     (x, y) against the diagonal of opposite slope, decided by four orientation signs
 //     (RobustLineIntersector; jts_orientation, gm_device.hpp) -- reached only when both endpoints are
@@ -50,7 +53,31 @@ __device__ __forceinline__ bool pt_in_seg_env(double ax, double ay, double bx, d
          qy <= (ay > by ? ay : by);
 }
 
-// RectangleLineIntersector.intersects(p0, p1) for a non-null box
+// RobustLineIntersector.computeIntersect(p1, p2, q1, q2).hasIntersection() past its envelope test
+__device__ __forceinline__ bool segs_cross(double ax, double ay, double bx, double by, double cx, double cy,
+                                           double dx, double dy) {
+  const int pq1 = jts_orientation(ax, ay, bx, by, cx, cy);
+  const int pq2 = jts_orientation(ax, ay, bx, by, dx, dy);
+  if ((pq1 > 0 && pq2 > 0) || (pq1 < 0 && pq2 < 0)) return false;
+  const int qp1 = jts_orientation(cx, cy, dx, dy, ax, ay);
+  const int qp2 = jts_orientation(cx, cy, dx, dy, bx, by);
+  if ((qp1 > 0 && qp2 > 0) || (qp1 < 0 && qp2 < 0)) return false;
+  if ((pq1 | pq2 | qp1 | qp2) == 0)   // computeCollinearIntersection
+    return pt_in_seg_env(ax, ay, bx, by, cx, cy) || pt_in_seg_env(ax, ay, bx, by, dx, dy) ||
+           pt_in_seg_env(cx, cy, dx, dy, ax, ay) || pt_in_seg_env(cx, cy, dx, dy, bx, by);
+  return true;
+}
+
+__device__ __forceinline__ bool seg_meets_seg(double ax, double ay, double bx, double by, double cx, double cy,
+                                              double dx, double dy) {
+  if ((ax < bx ? ax : bx) > (cx > dx ? cx : dx) || (ax > bx ? ax : bx) < (cx < dx ? cx : dx) ||
+      (ay < by ? ay : by) > (cy > dy ? cy : dy) || (ay > by ? ay : by) < (cy < dy ? cy : dy))
+    return false;
+  return segs_cross(ax, ay, bx, by, cx, cy, dx, dy);
+}
+
+// RectangleLineIntersector.intersects(p0, p1) for a non-null box: its two cheap tests, then the segment
+// against a diagonal, whose envelope is the box (so seg_meets_seg's envelope test is the first one here)
 __device__ __forceinline__ bool seg_meets_box(double ax, double ay, double bx, double by, const Box& q) {
   const double sx0 = ax < bx ? ax : bx, sx1 = ax > bx ? ax : bx;
   const double sy0 = ay < by ? ay : by, sy1 = ay > by ? ay : by;
@@ -62,195 +89,142 @@ __device__ __forceinline__ bool seg_meets_box(double ax, double ay, double bx, d
     t = ay; ay = by; by = t;
   }
   const bool up = by > ay;
-  const double d0x = q.x0, d0y = up ? q.y1 : q.y0, d1x = q.x1, d1y = up ? q.y0 : q.y1;
-  // RobustLineIntersector.computeIntersect (the envelopes overlap: the diagonal's is the box)
-  const int pq1 = jts_orientation(ax, ay, bx, by, d0x, d0y);
-  const int pq2 = jts_orientation(ax, ay, bx, by, d1x, d1y);
-  if ((pq1 > 0 && pq2 > 0) || (pq1 < 0 && pq2 < 0)) return false;
-  const int qp1 = jts_orientation(d0x, d0y, d1x, d1y, ax, ay);
-  const int qp2 = jts_orientation(d0x, d0y, d1x, d1y, bx, by);
-  if ((qp1 > 0 && qp2 > 0) || (qp1 < 0 && qp2 < 0)) return false;
-  if ((pq1 | pq2 | qp1 | qp2) == 0)   // computeCollinearIntersection
-    return pt_in_seg_env(ax, ay, bx, by, d0x, d0y) || pt_in_seg_env(ax, ay, bx, by, d1x, d1y) ||
-           pt_in_seg_env(d0x, d0y, d1x, d1y, ax, ay) || pt_in_seg_env(d0x, d0y, d1x, d1y, bx, by);
-  return true;
+  return segs_cross(ax, ay, bx, by, q.x0, up ? q.y1 : q.y0, q.x1, up ? q.y0 : q.y1);
 }
 
-// a List offset every lane of the wave reads alike, as a scalar
-__device__ __forceinline__ int32_t uoff(const int32_t* __restrict__ o, int64_t i) {
-  return __builtin_amdgcn_readfirstlane(o[i]);
+__device__ __forceinline__ double uniform(double v) {   // v, the same in every lane, as a scalar
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), lo);
 }
 
-// the tuples of a typed column as a tuple source (a WKB run is the other one: WkbTuples, gm_wkb.hpp)
-template <bool F32>
-struct ArrowTuples {
-  const void* c;
-  int flip;
-  __device__ __forceinline__ void tuple(int64_t j, double& x, double& y) const { arrow_tuple<F32>(c, j, flip, x, y); }
-};
-template <bool F32>
-__device__ __forceinline__ ArrowTuples<F32> tuples_of(const ArrowGeom& g) { return ArrowTuples<F32>{g.c, g.flip}; }
-
-// the tuples [a, b) as points: some point in the box
-template <class SRC>
-__device__ bool points_meet(const SRC& g, int32_t a, int32_t b, int lane, const Box& q) {
-  for (int32_t j0 = a; j0 < b; j0 += 64) {
+// the tuples [0, n) as points, spread over the lanes: f(x, y) of some point
+template <class SRC, class F>
+__device__ __forceinline__ bool points_any(const SRC& t, int32_t n, int lane, const F& f) {
+  for (int32_t j0 = 0; j0 < n; j0 += 64) {
     const int32_t j = j0 + lane;
     bool h = false;
-    if (j < b) {
+    if (j < n) {
       double x, y;
-      g.tuple(j, x, y);
-      h = pt_in_box(x, y, q);
+      t.tuple(j, x, y);
+      h = f(x, y);
     }
     if (__any(h)) return true;
   }
   return false;
 }
 
-// the tuples [a, b) as a line or a ring: some segment (j, j + 1), a <= j < b - 1, meets the box.  A wave
-// step reads one contiguous run of 64 tuples, one per lane, and takes each segment's second end from the
-// next lane, so a step covers 63 segments and no tuple is loaded twice within it.  RING also counts the
-// crossings of the corner (q.x0, q.y0) (on a segment: a hit) and gives the ring's parity
-template <bool RING, class SRC>
-__device__ bool line_meets(const SRC& g, int32_t a, int32_t b, int lane, const Box& q, bool& inside) {
-  int cross = 0;
-  for (int32_t j0 = a; j0 < b - 1; j0 += 63) {
-    const int32_t j = j0 + lane;
+// the tuples [0, n) as a line or a ring: f(ax, ay, bx, by) of some segment (j, j + 1), 0 <= j < n - 1.  A
+// wave step reads one contiguous run of 64 tuples, one per lane, and takes each segment's second end from
+// the next lane, so a step covers 63 segments and no tuple is loaded twice within it.  f keeps what a ring's
+// pass counts (crossings) in its own state, one count per lane
+template <class SRC, class F>
+__device__ __forceinline__ bool segments_any(const SRC& t, int32_t n, int lane, F& f) {
+  for (int32_t j0 = 0; j0 < n - 1; j0 += 63) {
+    const int32_t left = n - j0;   // wave-uniform: the lanes compare against it, the index stays base + lane
     double ax = 0.0, ay = 0.0;
-    if (j < b) g.tuple(j, ax, ay);
+    if (lane < left) t.tuple(j0 + lane, ax, ay);
     const double bx = __shfl_down(ax, 1, 64), by = __shfl_down(ay, 1, 64);
     bool h = false;
-    if (lane < 63 && j < b - 1) {
-      h = seg_meets_box(ax, ay, bx, by, q);
-      if (RING && !h) h = count_segment(ax, ay, bx, by, q.x0, q.y0, cross);
-    }
+    if (lane < 63 && lane < left - 1) h = f(ax, ay, bx, by);
     if (__any(h)) return true;
   }
-  if (RING) inside = __popcll(__ballot(cross & 1)) & 1;
   return false;
 }
 
-// the rings [r0, r1) of `ro` as one polygon, shell first: a ring segment meets the box, or the box's
-// corner is inside the shell and inside no hole (SimplePointInAreaLocator.locatePointInPolygon)
-template <class SRC>
-__device__ bool polygon_meets(const SRC& g, const int32_t* __restrict__ ro, int32_t r0, int32_t r1, int lane,
-                              const Box& q) {
-  bool in_shell = false, in_hole = false;
-  for (int32_t r = r0; r < r1; ++r) {
-    bool in = false;
-    if (line_meets<true>(g, uoff(ro, r), uoff(ro, r + 1), lane, q, in)) return true;
-    if (r == r0) in_shell = in; else in_hole |= in;
+// a segment against the box; RING also counts the crossings of the corner (q.x0, q.y0) (on a segment: a hit)
+template <bool RING>
+struct BoxSeg {
+  const Box& q;
+  int cross;
+  __device__ __forceinline__ bool operator()(double ax, double ay, double bx, double by) {
+    bool h = seg_meets_box(ax, ay, bx, by, q);
+    if (RING && !h) h = count_segment(ax, ay, bx, by, q.x0, q.y0, cross);
+    return h;
   }
-  return in_shell && !in_hole;
-}
+};
 
-// slot i meets the box (wave-uniform; every lane of the wave calls it with the same i and q)
-template <bool F32>
-__device__ bool geom_meets_box(const ArrowGeom& g, int64_t i, int lane, const Box& q) {
-  bool unused;
-  const ArrowTuples<F32> ts = tuples_of<F32>(g);
-  switch (g.type) {
-    case GM_GEOM_POINT: {
-      double x, y;
-      arrow_tuple<F32>(g.c, i, g.flip, x, y);
-      return pt_in_box(x, y, q);
-    }
-    case GM_GEOM_MULTIPOINT:
-      return points_meet(ts, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
-    case GM_GEOM_LINESTRING:
-      return line_meets<false>(ts, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q, unused);
-    case GM_GEOM_POLYGON:
-      return polygon_meets(ts, g.o1, uoff(g.o0, i), uoff(g.o0, i + 1), lane, q);
-    case GM_GEOM_MULTILINESTRING: {
-      const int32_t l1 = uoff(g.o0, i + 1);
-      for (int32_t l = uoff(g.o0, i); l < l1; ++l)
-        if (line_meets<false>(ts, uoff(g.o1, l), uoff(g.o1, l + 1), lane, q, unused)) return true;
-      return false;
-    }
-    default: {   // GM_GEOM_MULTIPOLYGON
-      const int32_t p1 = uoff(g.o0, i + 1);
-      for (int32_t p = uoff(g.o0, i); p < p1; ++p)
-        if (polygon_meets(ts, g.o2, uoff(g.o1, p), uoff(g.o1, p + 1), lane, q)) return true;
-      return false;
-    }
-  }
-}
-
-// A WKB slot against the box, the whole wave on one slot (wkb_walk<true>): each class decided as
-// geom_meets_box decides it, a collection by any of its elements; the walk stops at the first hit.  A
-// LineString of one tuple is that point.  A MultiPoint's points each carry a header of their own, so they
-// are taken one per step, every lane alike.
-struct WkbMeets {
+// A slot against the box, the whole wave on it (UNI walks): a collection by any of its elements; the walk
+// stops at the first hit
+struct MeetsBox {
   Box q;
   int lane;
   bool in_shell, in_hole;
-  __device__ __forceinline__ bool point(const WkbTuples& t) {
+  template <class T>
+  __device__ __forceinline__ bool point(const T& t) {
     double x, y;
     t.tuple(0, x, y);
     return pt_in_box(x, y, q);
   }
-  __device__ __forceinline__ bool line(const WkbTuples& t, uint32_t n) {
-    bool unused;
-    return n == 1 ? point(t) : line_meets<false>(t, 0, (int32_t)n, lane, q, unused);
+  template <class T>
+  __device__ __forceinline__ bool points(const T& t, int32_t n) {
+    const auto in = [&](double x, double y) __attribute__((always_inline)) { return pt_in_box(x, y, q); };
+    return points_any(t, n, lane, in);
+  }
+  // A WKB LineString of one tuple is that point.  A typed one has no segment and meets nothing here; alone
+  // in its slot it matches all the same, by the envelope shortcut (its envelope is the point)
+  template <class T>
+  __device__ __forceinline__ bool line(const T& t, int32_t n) {
+    if (T::WKB && n == 1) return point(t);
+    BoxSeg<false> f{q, 0};
+    return segments_any(t, n, lane, f);
   }
   __device__ __forceinline__ void polygon_begin() { in_shell = in_hole = false; }
-  __device__ __forceinline__ bool ring(uint32_t r, const WkbTuples& t, uint32_t n) {
-    bool in = false;
-    if (line_meets<true>(t, 0, (int32_t)n, lane, q, in)) return true;
+  template <class T>
+  __device__ __forceinline__ bool ring(uint32_t r, const T& t, int32_t n) {
+    BoxSeg<true> f{q, 0};
+    if (segments_any(t, n, lane, f)) return true;
+    const bool in = __popcll(__ballot(f.cross & 1)) & 1;
     if (r == 0) in_shell = in; else in_hole |= in;
     return false;
   }
+  // no ring segment met the box: its corner inside the shell and inside no hole
+  // (SimplePointInAreaLocator.locatePointInPolygon)
   __device__ __forceinline__ bool polygon_end() { return in_shell && !in_hole; }
 };
 
-// WKB: the column is GM_GEOM_WKB (F32 false).  The shortcuts go by the slot's top-level code; a malformed
-// slot never matches (its envelope column holds the null envelope, so it is not even walked)
-template <bool F32, bool WKB>
-__global__ __launch_bounds__(GTPB) void k_geom_refine(ArrowGeom g, GeomRefine a) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t nwaves = (int64_t)gridDim.x * (GTPB / 64);
-  bool connected = g.type == GM_GEOM_LINESTRING || g.type == GM_GEOM_POLYGON;
-  __shared__ uint32_t s_rem[WKB ? WKB_DEPTH * (GTPB / 64) : 1];   // wkb_walk's stack, one column per wave
-  for (int64_t s = (int64_t)blockIdx.x * (GTPB / 64) + wave; s < a.n_surv; s += nwaves) {
-    const int64_t c = a.surv[s];
-    const int64_t row = cand_row(a.coff, a.start, a.nr, c);
-    const int64_t r = a.rows ? a.rows[row] : row;
-    bool hit = false;
-    bool valid = arrow_valid(g.valid, g.voff, r);
-    if (WKB && valid) {
+// The box filter as k_refine's predicate: the box loop and the two envelope shortcuts
+struct BoxPred {
+  const double* boxes;   // nbox x (xmin, ymin, xmax, ymax)
+  int nbox;
+  template <bool F32, bool WKB>
+  __device__ __forceinline__ bool meets(const ArrowGeom& g, int64_t r, double ex0, double ey0, double ex1, double ey1,
+                                        int lane, uint32_t* rem) const {
+    // one connected component: by the column's type, and for WKB by the slot's own top-level code (a
+    // malformed slot never matches; its envelope column holds the null envelope besides)
+    bool connected = g.type == GM_GEOM_LINESTRING || g.type == GM_GEOM_POLYGON;
+    if (WKB) {
       WkbCur top = wkb_slot(g, r);
       WkbHead h;
-      valid = wkb_head<true>(top, h);
-      connected = valid && (h.code == WKB_LINESTRING || h.code == WKB_POLYGON);
+      if (!wkb_head<true>(top, h)) return false;
+      connected = h.code == WKB_LINESTRING || h.code == WKB_POLYGON;
     }
-    if (valid) {
-      const double ex0 = a.xmin[r], ey0 = a.ymin[r], ex1 = a.xmax[r], ey1 = a.ymax[r];
-      for (int k = 0; k < a.nbox && !hit; ++k) {
-        const double* b = a.boxes + 4 * k;
-        if (!env_intersects(ex0, ey0, ex1, ey1, b)) continue;
-        const Box q{b[0], b[1], b[2], b[3]};
-        const bool xin = ex0 >= q.x0 && ex1 <= q.x1, yin = ey0 >= q.y0 && ey1 <= q.y1;
-        hit = (xin && yin) || (connected && (xin || yin));
-        if (hit) continue;
-        if (WKB) {
-          WkbMeets v{q, lane, false, false};
-          hit = wkb_walk<true>(wkb_slot(g, r), s_rem + wave, GTPB / 64, v) == WKB_STOP;
-        } else {
-          hit = geom_meets_box<F32>(g, r, lane, q);
-        }
-      }
+    bool hit = false;
+    for (int k = 0; k < nbox && !hit; ++k) {
+      const double* b = boxes + 4 * k;
+      if (!env_intersects(ex0, ey0, ex1, ey1, b)) continue;
+      // in scalar registers: as vector ones the box is what takes the typed kernel past 80 VGPRs (6 waves)
+      const Box q{uniform(b[0]), uniform(b[1]), uniform(b[2]), uniform(b[3])};
+      const bool xin = ex0 >= q.x0 && ex1 <= q.x1, yin = ey0 >= q.y0 && ey1 <= q.y1;
+      hit = (xin && yin) || (connected && (xin || yin));
+      if (hit) continue;
+      MeetsBox v{q, lane, false, false};
+      hit = geom_walk<true, F32, WKB>(g, r, rem, GTPB / 64, v) == WKB_STOP;
     }
-    if (!hit && lane == 0) atomicAnd((unsigned long long*)&a.mask[c >> 6], ~(1ull << (c & 63)));
+    return hit;
   }
-}
+};
 
 // ------------------------------------------------------------------ geometry meets query polygons
+// NOT merged into k_refine and the shared walk: as a predicate with a visitor under arrow_walk / wkb_walk and
+// run_meets_a over segments_any it gave the same ids with 112-114 VGPRs for 105-107 and took 3.5% longer where
+// it dominates ("Geometry walks and visitors").  Its kernel, typed switch and WKB visitor stay; the
+// price is a second tuple source for a typed column (ArrowColumn) and a second scalar offset read (uoff).
+//
 // k_poly_refine: INTERSECTS(geom, polygons), the contract of geomesa_hip.h.  Still one wave per envelope
 // survivor.  The query (PolyQuery, gm_scan.hpp) is its ring edges bucketed by y-slab; while the entries fit
 // PQ_LDS_ENTRIES they are staged in LDS once per workgroup, else read from global memory (L2).  Per tuple
 // run of G (a line, or a ring) the pair space is G's segments x the query's entries, in one of two shapes:
-//   * run_meets_a, 64 tuples or more: lanes stride over G's segments (line_meets' read pattern) and each
+//   * run_meets_a, more than 64 tuples: lanes stride over G's segments (segments_any's read pattern) and each
 //     lane loops the entries of the slabs its own segment's y-range overlaps;
 //   * run_meets_b, fewer segments than a wave: the run sits in registers, one tuple per lane; lanes stride
 //     over the entries of the slabs the SLOT's y-range overlaps (one contiguous run) and loop G's
@@ -266,6 +240,17 @@ constexpr int PQ_MAX_BLOCKS = 1024;    // a staging workgroup strides over the s
 
 extern __shared__ __attribute__((aligned(16))) char pq_smem[];
 
+// a List offset every lane of the wave reads alike, as a scalar
+__device__ __forceinline__ int32_t uoff(const int32_t* o, int64_t i) { return __builtin_amdgcn_readfirstlane(o[i]); }
+
+// the whole typed column as a tuple source, indexed from its tuple 0 (ArrowTuples carries a run's base)
+template <bool F32>
+struct ArrowColumn {
+  const void* c;
+  int flip;
+  __device__ __forceinline__ void tuple(int64_t j, double& x, double& y) const { arrow_tuple<F32>(c, j, flip, x, y); }
+};
+
 template <bool LDS>
 struct QEdges {
   const double* g;
@@ -279,24 +264,6 @@ struct QEdges {
 __device__ __forceinline__ int pq_slab(double y, const PolyQuery& q) {   // polyq::slab_of
   const double c = floor(__dmul_rn(__dsub_rn(y, q.y0), q.inv_h));
   return (int)__builtin_fmin(__builtin_fmax(c, 0.0), (double)(q.ns - 1));
-}
-
-// RobustLineIntersector.computeIntersect(p1, p2, q1, q2).hasIntersection()
-__device__ __forceinline__ bool seg_meets_seg(double ax, double ay, double bx, double by, double cx, double cy,
-                                              double dx, double dy) {
-  if ((ax < bx ? ax : bx) > (cx > dx ? cx : dx) || (ax > bx ? ax : bx) < (cx < dx ? cx : dx) ||
-      (ay < by ? ay : by) > (cy > dy ? cy : dy) || (ay > by ? ay : by) < (cy < dy ? cy : dy))
-    return false;
-  const int pq1 = jts_orientation(ax, ay, bx, by, cx, cy);
-  const int pq2 = jts_orientation(ax, ay, bx, by, dx, dy);
-  if ((pq1 > 0 && pq2 > 0) || (pq1 < 0 && pq2 < 0)) return false;
-  const int qp1 = jts_orientation(cx, cy, dx, dy, ax, ay);
-  const int qp2 = jts_orientation(cx, cy, dx, dy, bx, by);
-  if ((qp1 > 0 && qp2 > 0) || (qp1 < 0 && qp2 < 0)) return false;
-  if ((pq1 | pq2 | qp1 | qp2) == 0)   // computeCollinearIntersection
-    return pt_in_seg_env(ax, ay, bx, by, cx, cy) || pt_in_seg_env(ax, ay, bx, by, dx, dy) ||
-           pt_in_seg_env(cx, cy, dx, dy, ax, ay) || pt_in_seg_env(cx, cy, dx, dy, bx, by);
-  return true;
 }
 
 // one survivor's view of the query: the slot's envelope, the entries of the slabs it overlaps, and the
@@ -499,7 +466,7 @@ __device__ __forceinline__ bool points_meet_polys(const SRC& g, int32_t a, int32
 // slot i meets a part (wave-uniform), for the group of parts c holds
 template <bool F32, bool LDS>
 __device__ __forceinline__ bool geom_meets_polys(const ArrowGeom& g, int64_t i, const PolyCtx<LDS>& c) {
-  const ArrowTuples<F32> ts = tuples_of<F32>(g);
+  const ArrowColumn<F32> ts{g.c, g.flip};
   switch (g.type) {
     case GM_GEOM_POINT:
       return c.contact && first_tuple_in(ts, i, c);
@@ -593,6 +560,27 @@ __global__ __launch_bounds__(GTPB) void k_poly_refine(ArrowGeom g, GeomRefine a,
   }
 }
 
+// ------------------------------------------------------------------ the kernels
+// One wave per survivor: candidate -> table row -> column row, a null slot never matches, else the
+// predicate P (BoxPred) decides on the slot and its envelope; a miss clears the candidate's bit.  WKB: the
+// column is GM_GEOM_WKB (F32 false)
+template <bool F32, bool WKB, class P>
+__global__ __launch_bounds__(GTPB) void k_refine(ArrowGeom g, GeomRefine a, P p) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t nwaves = (int64_t)gridDim.x * (GTPB / 64);
+  __shared__ uint32_t s_rem[WKB ? WKB_DEPTH * (GTPB / 64) : 1];   // wkb_walk's stack, one column per wave
+  uint32_t* rem = s_rem + wave;
+  for (int64_t s = (int64_t)blockIdx.x * (GTPB / 64) + wave; s < a.n_surv; s += nwaves) {
+    const int64_t c = a.surv[s];
+    const int64_t row = cand_row(a.coff, a.start, a.nr, c);
+    const int64_t r = a.rows ? a.rows[row] : row;
+    const bool hit = arrow_valid(g.valid, g.voff, r) &&
+                     p.template meets<F32, WKB>(g, r, a.xmin[r], a.ymin[r], a.xmax[r], a.ymax[r], lane, rem);
+    if (!hit && lane == 0) atomicAnd((unsigned long long*)&a.mask[c >> 6], ~(1ull << (c & 63)));
+  }
+}
+
 // per-block match counts of a candidate mask (the block_counts of pass A), one wave per block
 __global__ __launch_bounds__(64) void k_mask_recount(const uint64_t* __restrict__ mask, int64_t total,
                                                      int32_t* __restrict__ counts) {
@@ -606,28 +594,16 @@ __global__ __launch_bounds__(64) void k_mask_recount(const uint64_t* __restrict_
   if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
-// Geometry.getEnvelopeInternal of every slot; a null slot reads as the null envelope
-template <bool F32>
-__global__ __launch_bounds__(GTPB) void k_arrow_envelopes(ArrowGeom g, int64_t n, double* __restrict__ xmin,
-                                                          double* __restrict__ ymin, double* __restrict__ xmax,
-                                                          double* __restrict__ ymax) {
-  for (int64_t i = (int64_t)blockIdx.x * GTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GTPB) {
-    const Env e = arrow_valid(g.valid, g.voff, i) ? geom_envelope<F32>(g, i) : env_null();
-    xmin[i] = e.minx;
-    ymin[i] = e.miny;
-    xmax[i] = e.maxx;
-    ymax[i] = e.maxy;
-  }
-}
-
-// the same over a GM_GEOM_WKB column: one lane walks one slot's bytes (gm_wkb.hpp)
-__global__ __launch_bounds__(GTPB) void k_wkb_envelopes(ArrowGeom g, int64_t n, double* __restrict__ xmin,
-                                                        double* __restrict__ ymin, double* __restrict__ xmax,
-                                                        double* __restrict__ ymax) {
-  __shared__ uint32_t s_rem[WKB_DEPTH * GTPB];
+// Geometry.getEnvelopeInternal of every slot, one lane per slot; a null slot, and a malformed WKB one,
+// reads as the null envelope
+template <bool F32, bool WKB>
+__global__ __launch_bounds__(GTPB) void k_envelopes(ArrowGeom g, int64_t n, double* __restrict__ xmin,
+                                                    double* __restrict__ ymin, double* __restrict__ xmax,
+                                                    double* __restrict__ ymax) {
+  __shared__ uint32_t s_rem[WKB ? WKB_DEPTH * GTPB : 1];   // wkb_walk's stack, one column per lane
   for (int64_t i = (int64_t)blockIdx.x * GTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GTPB) {
     Env e = env_null();
-    if (arrow_valid(g.valid, g.voff, i)) wkb_envelope(g, i, s_rem + threadIdx.x, GTPB, e);
+    if (arrow_valid(g.valid, g.voff, i)) slot_envelope<F32, WKB>(g, i, s_rem + threadIdx.x, GTPB, e);
     xmin[i] = e.minx;
     ymin[i] = e.miny;
     xmax[i] = e.maxx;
@@ -640,16 +616,33 @@ static ArrowGeom to_geom(const gm_geom_column* c) {
                    c->flip_axis};
 }
 
-int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a) {
+// f(F32, WKB) as template flags; a WKB column holds doubles
+template <class F>
+static void with_column_form(const gm_geom_column* geom, F&& f) {
+  const bool wkb = geom->type == GM_GEOM_WKB;
+  with_flags([&](auto F32, auto WKB) {
+    if constexpr (!(F32() && WKB())) f(F32, WKB);
+  }, geom->ordinal_bits == 32 && !wkb, wkb);
+}
+
+int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a, const PolyQuery* q) {
   const ArrowGeom g = to_geom(geom);
-  const int64_t blocks = std::min<int64_t>((a.n_surv + GTPB / 64 - 1) / (GTPB / 64), 1 << 20);
-  if (geom->type == GM_GEOM_WKB) {
-    hipLaunchKernelGGL((k_geom_refine<false, true>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, a);
-  } else {
-    with_flags([&](auto F) {
-      hipLaunchKernelGGL((k_geom_refine<F(), false>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, a);
-    }, geom->ordinal_bits == 32);
-  }
+  const bool lds = q && q->entries <= PQ_LDS_ENTRIES;
+  const int64_t blocks = std::min<int64_t>((a.n_surv + GTPB / 64 - 1) / (GTPB / 64), lds ? PQ_MAX_BLOCKS : 1 << 20);
+  // the polygon kernel's dynamic LDS: the staged entries, then the WKB stack (the box kernel's is static)
+  const size_t smem = !q ? 0 : (lds ? (size_t)q->entries * 32 : 0) +
+                                   (geom->type == GM_GEOM_WKB ? WKB_DEPTH * (GTPB / 64) * sizeof(uint32_t) : 0);
+  with_column_form(geom, [&](auto F32, auto WKB) {
+    if (!q) {
+      hipLaunchKernelGGL((k_refine<decltype(F32)::value, decltype(WKB)::value, BoxPred>), dim3((unsigned)blocks),
+                         dim3(GTPB), 0, ctx->stream, g, a, BoxPred{a.boxes, a.nbox});
+    } else {
+      with_flags([&](auto LDS) {
+        hipLaunchKernelGGL((k_poly_refine<decltype(F32)::value, decltype(WKB)::value, decltype(LDS)::value>),
+                           dim3((unsigned)blocks), dim3(GTPB), smem, ctx->stream, g, a, *q);
+      }, lds);
+    }
+  });
   GM_CHECK_LAUNCH();
   const int64_t nblocks = (a.total + FROWS - 1) / FROWS;
   hipLaunchKernelGGL(k_mask_recount, dim3((unsigned)nblocks), dim3(64), 0, ctx->stream, a.mask, a.total, a.counts);
@@ -676,22 +669,6 @@ int upload_polys(gm_ctx* ctx, DevTemps& tmp, const polyq::HostQuery& h, PolyQuer
   return GM_OK;
 }
 
-int poly_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a, const PolyQuery& q) {
-  const ArrowGeom g = to_geom(geom);
-  const bool lds = q.entries <= PQ_LDS_ENTRIES, wkb = geom->type == GM_GEOM_WKB;
-  const int64_t blocks = std::min<int64_t>((a.n_surv + GTPB / 64 - 1) / (GTPB / 64), lds ? PQ_MAX_BLOCKS : 1 << 20);
-  const size_t smem = (lds ? (size_t)q.entries * 32 : 0) + (wkb ? WKB_DEPTH * (GTPB / 64) * sizeof(uint32_t) : 0);
-  with_flags([&](auto F, auto W, auto L) {
-    if constexpr (!(F() && W()))   // a WKB column holds doubles
-      hipLaunchKernelGGL((k_poly_refine<F(), W(), L()>), dim3((unsigned)blocks), dim3(GTPB), smem, ctx->stream, g, a, q);
-  }, geom->ordinal_bits == 32 && !wkb, wkb, lds);
-  GM_CHECK_LAUNCH();
-  const int64_t nblocks = (a.total + FROWS - 1) / FROWS;
-  hipLaunchKernelGGL(k_mask_recount, dim3((unsigned)nblocks), dim3(64), 0, ctx->stream, a.mask, a.total, a.counts);
-  GM_CHECK_LAUNCH();
-  return GM_OK;
-}
-
 }  // namespace gm
 
 using namespace gm;
@@ -706,15 +683,10 @@ int gm_arrow_envelopes(gm_ctx* ctx, const gm_geom_column* geom, int64_t n, doubl
   GM_HIP(hipSetDevice(ctx->device));
   const ArrowGeom g = to_geom(geom);
   const int64_t blocks = std::min<int64_t>((n + GTPB - 1) / GTPB, 256 * 32);
-  if (geom->type == GM_GEOM_WKB) {
-    hipLaunchKernelGGL(k_wkb_envelopes, dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, n, xmin, ymin, xmax,
-                       ymax);
-  } else {
-    with_flags([&](auto F) {
-      hipLaunchKernelGGL((k_arrow_envelopes<F()>), dim3((unsigned)blocks), dim3(GTPB), 0, ctx->stream, g, n, xmin,
-                         ymin, xmax, ymax);
-    }, geom->ordinal_bits == 32);
-  }
+  with_column_form(geom, [&](auto F32, auto WKB) {
+    hipLaunchKernelGGL((k_envelopes<decltype(F32)::value, decltype(WKB)::value>), dim3((unsigned)blocks), dim3(GTPB),
+                       0, ctx->stream, g, n, xmin, ymin, xmax, ymax);
+  });
   GM_CHECK_LAUNCH();
   return GM_OK;
 }

@@ -322,9 +322,10 @@ __device__ __forceinline__ bool env_intersects(double ax0, double ay0, double ax
   return !(q[0] > ax1 || q[2] < ax0 || q[1] > ay1 || q[3] < ay0);
 }
 
-// The exact full filter of gm_table_scan_geom (gm_geom_filter.hip) over the survivors of the envelope
-// pass: candidate surv[s] keeps its bit of `mask` iff its geometry slot meets one of the boxes; then
-// the per-block counts are taken again from the mask, so finish_scan runs on it as on pass A's output.
+// The exact full filter of gm_table_scan_geom (geom_refine, gm_geom_filter.hip) over the survivors of the
+// envelope pass: candidate surv[s] keeps its bit of `mask` iff its geometry slot meets one of the boxes --
+// or, given query polygons, one of their parts; then the per-block counts are taken again from the mask, so
+// finish_scan runs on it as on pass A's output.
 struct GeomRefine {
   const int64_t* surv;                          // surviving candidate indices, ascending
   int64_t n_surv;
@@ -337,7 +338,6 @@ struct GeomRefine {
   uint64_t* mask;
   int32_t* counts;
 };
-int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a);
 
 // The query polygons of gm_scan_filter.polys on the device (gm_poly_query_host.hpp builds them): the ring
 // edges bucketed by y-slab, each entry with its coordinates, its ring and its part * 2 + shell flag, and
@@ -352,7 +352,7 @@ struct PolyQuery {
 };
 // the host images into `tmp`, one copy (synchronises the stream)
 int upload_polys(gm_ctx* ctx, DevTemps& tmp, const polyq::HostQuery& h, PolyQuery& q);
-// geom_refine against the query polygons: candidate surv[s] keeps its bit iff its slot meets a part
-int poly_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a, const PolyQuery& q);
+// q null: against a.boxes; else against the query polygons (a.boxes, the parts' envelopes, are not read)
+int geom_refine(gm_ctx* ctx, const gm_geom_column* geom, const GeomRefine& a, const PolyQuery* q);
 
 }  // namespace gm

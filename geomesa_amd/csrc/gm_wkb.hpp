@@ -5,12 +5,13 @@
 //   * WkbCur: a slot's bytes [p, end).  Every read goes through wkb_head / wkb_count / wkb_run, which
 //     compare what the header claims with the bytes that remain (count * stride in 64 bits) BEFORE the
 //     cursor moves, so no byte outside the slot is ever read, whatever the blob says;
-//   * wkb_walk: the traversal, shared by the three uses (envelopes and XZ keys, the point adapter's
-//     top-level read, the exact box filter).  Collections are walked with an explicit stack of the
-//     element counts still to read, GM_WKB_MAX_DEPTH levels deep, kept in LDS (a register array indexed
-//     by the depth would live in scratch); the code a Multi*'s elements must carry takes 4 bits per
-//     level of one register.  A visitor sees each point, line and ring as (first byte, tuple count,
-//     stride in bytes, byte order) and may stop the walk;
+//   * wkb_walk: the traversal, shared by its uses (envelopes and XZ keys, the exact box and polygon
+//     filters), with the visitor protocol of arrow_walk (gm_arrow.hpp): a decision can be written once, as a
+//     visitor templated on the tuple source, and serves both column forms.  Collections are walked with
+//     an explicit stack of the element counts still to read, GM_WKB_MAX_DEPTH levels deep, kept in LDS (a
+//     register array indexed by the depth would live in scratch); the code a Multi*'s elements must carry
+//     takes 4 bits per level of one register.  A visitor sees each point, line and ring as a WkbTuples
+//     (first byte, stride in bytes, byte order) with its tuple count, and may stop the walk;
 //   * UNI: the caller is a whole wave on one slot; headers and counts then go through readfirstlane so
 //     the walk's control flow stays scalar.
 // Ordinates are moved as 64-bit integers from unaligned addresses (memcpy: slots start at any byte),
@@ -105,8 +106,9 @@ __device__ __forceinline__ bool wkb_run(WkbCur& c, uint32_t n, uint32_t stride, 
   return true;
 }
 
-// a tuple run as the exact filter's tuple source (points_meet / line_meets, gm_geom_filter.hip)
+// a tuple run as a tuple source, from its first byte on (a typed column's: ArrowTuples, gm_arrow.hpp)
 struct WkbTuples {
+  static constexpr bool WKB = true;
   const uint8_t* base;
   uint32_t stride;
   bool le;
@@ -118,13 +120,15 @@ struct WkbTuples {
 };
 
 // Walks one slot.  rem[k * rs], k < WKB_DEPTH, is this walker's stack (LDS).  The visitor's point / line /
-// ring / polygon_end return true to stop the walk (WKB_STOP):
-//   point(t)        the tuple of a Point
+// ring / polygon_end return true to stop the walk (WKB_STOP); the protocol is arrow_walk's (gm_arrow.hpp),
+// so one visitor serves both column forms:
+//   point(t)        the tuple of a Point (a MultiPoint's points arrive here too, one per call)
 //   line(t, n)      the n tuples of a LineString
 //   polygon_begin() then ring(r, t, n) for each ring, shell first, then polygon_end()
-// with t a WkbTuples.  The shortest geometry is 9 bytes (an empty LineString, Polygon or collection) and
-// the shortest ring 4, so a count that cannot fit in the bytes left is malformed before its elements are
-// looked at; that also bounds the walk by the slot's length.
+// with t a WkbTuples and n < 2^27 (the slot's bytes bound it), handed over signed.  The shortest geometry is
+// 9 bytes (an empty LineString, Polygon or collection) and the shortest ring 4, so a count that cannot fit in
+// the bytes left is malformed before its elements are looked at; that also bounds the walk by the slot's
+// length.
 template <bool UNI, class V>
 __device__ __forceinline__ int wkb_walk(WkbCur c, uint32_t* rem, int rs, V& v) {
   int depth = 0;        // collections around the geometry being read
@@ -148,14 +152,14 @@ __device__ __forceinline__ int wkb_walk(WkbCur c, uint32_t* rem, int rs, V& v) {
       if (v.point(WkbTuples{base, h.stride, h.le})) return WKB_STOP;
     } else if (h.code == WKB_LINESTRING) {
       if (!wkb_count<UNI>(c, h.le, n) || !wkb_run(c, n, h.stride, base)) return WKB_BAD;
-      if (v.line(WkbTuples{base, h.stride, h.le}, n)) return WKB_STOP;
+      if (v.line(WkbTuples{base, h.stride, h.le}, (int32_t)n)) return WKB_STOP;
     } else if (h.code == WKB_POLYGON) {
       uint32_t nr;
       if (!wkb_count<UNI>(c, h.le, nr) || (uint64_t)nr * 4 > (uint64_t)c.left()) return WKB_BAD;
       v.polygon_begin();
       for (uint32_t r = 0; r < nr; ++r) {
         if (!wkb_count<UNI>(c, h.le, n) || !wkb_run(c, n, h.stride, base)) return WKB_BAD;
-        if (v.ring(r, WkbTuples{base, h.stride, h.le}, n)) return WKB_STOP;
+        if (v.ring(r, WkbTuples{base, h.stride, h.le}, (int32_t)n)) return WKB_STOP;
       }
       if (v.polygon_end()) return WKB_STOP;
     } else {   // MultiPoint, MultiLineString, MultiPolygon, GeometryCollection
@@ -170,43 +174,21 @@ __device__ __forceinline__ int wkb_walk(WkbCur c, uint32_t* rem, int rs, V& v) {
   }
 }
 
-// ------------------------------------------------------------------ envelopes
-// Geometry.getEnvelopeInternal with the rules gm_arrow.hpp restates: every element's own envelope
-// (CoordinateSequence.expandEnvelope: the first tuple initialises, strict compares after it), merged
-// skipping null ones; a polygon's is its shell's; a Point with a NaN x or y is the empty point.
-struct WkbEnvelope {
-  Env e;
-  __device__ __forceinline__ static Env of(const WkbTuples& t, uint32_t n) {
-    Env r = env_null();
-    for (uint32_t j = 0; j < n; ++j) {
-      double x, y;
-      t.tuple(j, x, y);
-      env_expand(r, x, y);
-    }
-    return r;
-  }
-  __device__ __forceinline__ bool point(const WkbTuples& t) {
-    double x, y;
-    t.tuple(0, x, y);
-    if (x == x && y == y) env_merge(e, Env{x, x, y, y, false});
-    return false;
-  }
-  __device__ __forceinline__ bool line(const WkbTuples& t, uint32_t n) {
-    env_merge(e, of(t, n));
-    return false;
-  }
-  __device__ __forceinline__ void polygon_begin() {}
-  __device__ __forceinline__ bool ring(uint32_t r, const WkbTuples& t, uint32_t n) {
-    if (r == 0) env_merge(e, of(t, n));
-    return false;
-  }
-  __device__ __forceinline__ bool polygon_end() { return false; }
-};
+// slot i of either column form through one call (rem / rs are unused by a typed column, whose slots are
+// never malformed)
+template <bool UNI, bool F32, bool WKB, class V>
+__device__ __forceinline__ int geom_walk(const ArrowGeom& g, int64_t i, uint32_t* rem, int rs, V& v) {
+  if constexpr (WKB) return wkb_walk<UNI>(wkb_slot(g, i), rem, rs, v);
+  else return arrow_walk<UNI, F32>(g, i, v) ? WKB_STOP : WKB_END;
+}
 
-// the envelope of slot i, one lane per slot; false: a malformed slot (e is then the null envelope)
-__device__ __forceinline__ bool wkb_envelope(const ArrowGeom& g, int64_t i, uint32_t* rem, int rs, Env& e) {
-  WkbEnvelope v{env_null()};
-  const bool ok = wkb_walk<false>(wkb_slot(g, i), rem, rs, v) != WKB_BAD;
+// ------------------------------------------------------------------ envelopes
+// Geometry.getEnvelopeInternal of slot i of either column form, one lane per slot (EnvelopeOf,
+// gm_arrow.hpp); false: a malformed WKB slot (e is then the null envelope)
+template <bool F32, bool WKB>
+__device__ __forceinline__ bool slot_envelope(const ArrowGeom& g, int64_t i, uint32_t* rem, int rs, Env& e) {
+  EnvelopeOf v{env_null()};
+  const bool ok = geom_walk<false, F32, WKB>(g, i, rem, rs, v) != WKB_BAD;
   e = ok ? v.e : env_null();
   return ok;
 }

@@ -124,6 +124,86 @@ def test_wkb_column_gives_the_typed_columns_ids(gpu, oracle, kind):
               P.envelope_hit(P.envelopes(kind), P.queries()[name]))
 
 
+# ---------------------------------------------------------------- the segment loop's step boundaries
+STEP_SIZES = (2, 3, 64, 65, 127, 128)     # tuples: within a step, exactly one step (63 segments), one segment
+STEP_HITS = (0, 62, 63, 125, 126)         # into the second, the third step's edge; hits at the steps' ends
+STEP_BOX = (-0.5, -1.5, 0.5, 1.5)         # about (0, 0), inside the concave query; narrower than a joining
+                                          # segment's x-extent, so no envelope shortcut settles a feature
+
+
+STEP_THROUGH, STEP_AROUND, STEP_ASIDE = (-1.0, 1.0), (9.0, 11.0), (-50.0, 10.0)
+
+
+def step_line(m, k, join):
+    """m tuples on two rails, y = -20 and y = 20, far from both queries; segment k alone joins the rails, from
+    (join[0], -20) to (join[1], 20): STEP_THROUGH runs it through the box and the concave query, STEP_ASIDE
+    clear of both on their left, under the feature's envelope all the same."""
+    return [(join[0] - 0.5 * (k - j), -20.0) if j <= k else (join[1] + 0.5 * (j - k - 1), 20.0) for j in range(m)]
+
+
+def step_ring(m, k, join):
+    """A closed ring of m >= 4 tuples: the same joining segment as segment k, the upper rail back to x = -80
+    and the lower rail from there.  It encloses what lies left of the joining segment, between the rails:
+    STEP_AROUND puts both queries inside with no segment near them, STEP_ASIDE both outside."""
+    n, nu = m - 1, (m - 2) // 2
+    nl = n - 2 - nu
+    w = [(join[0], -20.0), (join[1], 20.0)]
+    w += [(join[1] + (-80.0 - join[1]) * (i + 1) / nu, 20.0) for i in range(nu)]
+    w += [(-80.0 + (join[0] + 80.0) * i / nl, -20.0) for i in range(nl)]
+    ring = [w[(j - k) % n] for j in range(n)]
+    return ring + [ring[0]]
+
+
+@functools.lru_cache(maxsize=None)
+def step_rows(kind):
+    """(row, how many of its segments meet a query, match expected).  Rings of 2 and 3 tuples have no segment
+    of their own to single out ([a, a]; [a, b, a]): they go in with every segment a hit."""
+    rows = []
+    for m in STEP_SIZES:
+        hits = sorted({k for k in STEP_HITS + (m - 2,) if k <= m - 2})
+        if kind == "linestring":
+            rows += [(step_line(m, k, STEP_THROUGH), 1, True) for k in hits]
+            rows.append((step_line(m, hits[-1], STEP_ASIDE), 0, False))
+        elif m == 2:
+            rows.append(([[(0.25, 0.25), (0.25, 0.25)]], 1, True))
+        elif m == 3:
+            rows.append(([[(-1.0, -20.0), (1.0, 20.0), (-1.0, -20.0)]], 2, True))
+        else:   # and polygons that hold the queries, the one crossing counted at each of the same segments
+            rows += [([step_ring(m, k, STEP_THROUGH)], 1, True) for k in hits]
+            rows += [([step_ring(m, k, STEP_AROUND)], 0, True) for k in hits]
+            rows.append(([step_ring(m, m - 2, STEP_ASIDE)], 0, False))
+    return rows
+
+
+@pytest.mark.parametrize("form", ["typed", "wkb"])
+@pytest.mark.parametrize("kind", ["linestring", "polygon"])
+def test_one_hit_at_each_step_boundary(gpu, oracle, kind, form):
+    """Lines and single-ring polygons whose tuple counts sit at the edges of the 63-segment wave step, one
+    segment alone meeting the query, at segment 0, at a step's last and next step's first segment, and at the
+    final one; polygons that meet nothing and hold the box's corner / the query's first shell vertex, whose one
+    crossing is counted at each of those segments in turn.  The box filter sends every run through the shared
+    segment loop; the polygon filter only runs of more than 64 tuples (65, 127, 128 here), the shorter ones
+    going lanes-over-entries.  Only the [a, a] ring is settled by an envelope shortcut (it is a point)."""
+    import geom_intersects_ref as R
+    from geomesa_amd.table import XZ2Table
+    case = step_rows(kind)
+    rows = [r for r, _, _ in case]
+    q = P.queries()["concave"]
+    runs = [r if kind == "linestring" else r[0] for r in rows]
+    for run, (_, n_meet, exp) in zip(runs, case):      # the inputs, by the references alone
+        segs = list(zip(run, run[1:]))
+        assert sum(R.seg_meets_box(a, b, STEP_BOX) for a, b in segs) == n_meet
+        assert sum(P._contact([a, b], q) for a, b in segs) == n_meet or len(run) == 2   # [a, a] inside: no contact
+    exp = np.array([e for _, _, e in case])
+    assert np.array_equal(R.scan(rows, kind, [STEP_BOX]), exp)
+    assert np.array_equal(np.array([P.intersects_restated(r, kind, q) for r in rows]), exp)
+    arr, col = (to_arrow(rows, kind), kind) if form == "typed" else (wkb_array(rows, kind), "wkb")
+    tb = XZ2Table.from_geometries(arr, col)
+    for got in (tb.query([STEP_BOX]), tb.query(polygons=q.polygon_set())):
+        assert got[1] == exp.sum() and np.array_equal(np.sort(as_np(got[0])), np.nonzero(exp)[0])
+        assert tb.n_envelope == len(rows)              # every feature reaches the walk
+
+
 def collection_query():
     """Parts about the three sites of wkb_cases' mixed column: a star, a star with a hole, a rectangle; then
     six more small parts away from them, so that a polygon's first-vertex passes come in two groups."""

@@ -6,7 +6,7 @@ query of the exact box filter, and writes profiles/geom_poly_probe.json.
 The table is tools/wkb_probe.py's: n lines of 20 vertices, random walks about uniform centres, as a typed
 LineString column.  The queries, each timed with device events after a warm-up call (events around the
 whole call, its host steps, the query's upload and the count read-backs included):
-  box          the probe's box as a box: k_geom_refine, the baseline;
+  box          the probe's box as a box: k_refine with BoxPred, the baseline;
   rect5        the same rectangle as a 5-tuple polygon;
   ring65       a 65-tuple polygon of the same envelope (an ellipse touching the box's four sides);
   ring1000     a 1,000-tuple polygon of the same envelope;

@@ -10,7 +10,7 @@ each an arc about a uniform centre; one query box that about 1% of the envelopes
       parent commit, alternating, K rounds of `reps` calls each;
   (b) gm_table_scan_geom.
 The geometry result is checked on a strided sample of the envelope pass's survivors and of all features
-against tests/geom_intersects_ref.intersects_restated.  k_geom_refine's bytes model is the survivors' tuples
+against tests/geom_intersects_ref.intersects_restated.  The box filter's (k_refine, BoxPred) bytes model is the survivors' tuples
 x 16 B; its share of 8 TB/s is taken over (b) - (a), the time the geometry filter adds."""
 import ctypes
 import os

@@ -146,7 +146,7 @@ def main():
         ms, reps = timed(f)
         e = tables[kind].env
         meets = ~((e[2] < BOX[0]) | (e[0] > BOX[2]) | (e[3] < BOX[1]) | (e[1] > BOX[3]) | (e[2] < e[0]))
-        short = ((e[0] >= BOX[0]) & (e[2] <= BOX[2])) | ((e[1] >= BOX[1]) & (e[3] <= BOX[3]))   # k_geom_refine's shortcuts
+        short = ((e[0] >= BOX[0]) & (e[2] <= BOX[2])) | ((e[1] >= BOX[1]) & (e[3] <= BOX[3]))   # BoxPred's shortcuts
         row = {"entry": "XZ2Table.query(exact=True)", "column": kind, "ms": round(ms, 4), "reps": reps,
                "matches": int(nm), "envelope_survivors": int(tables[kind].n_envelope), "scanned": int(scanned),
                "survivors_walked": int((meets & ~short).sum().item())}
