@@ -46,19 +46,41 @@ __device__ __forceinline__ void arrow_time_pair(const ArrowTime& t, int64_t p, b
 
 // ------------------------------------------------------------------ Z3 / Z2 point keys
 
+// The store epilogue of the pair-strided kernels (a lane per rows 2p, 2p + 1, the odd last row a pair of
+// one): both rows as one 16-B / 4-B / 2-B store per column when `vec`, row by row otherwise.  bin: NULL
+// (folded) for the Z2 key.
+__device__ __forceinline__ void store_two_rows(bool vec, bool two, int64_t p, const int64_t* zz, const int16_t* b,
+                                               const uint8_t* st, int64_t* __restrict__ z, int16_t* __restrict__ bin,
+                                               uint8_t* __restrict__ status, int64_t* __restrict__ err) {
+  if (vec && two) {
+    st_stream(lv2{zz[0], zz[1]}, &((lv2*)z)[p]);
+    if (bin) ((short2*)bin)[p] = make_short2(b[0], b[1]);
+    if (status) ((uchar2*)status)[p] = make_uchar2(st[0], st[1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (j == 1 && !two) break;
+      z[2 * p + j] = zz[j];
+      if (bin) bin[2 * p + j] = b[j];
+      if (status) status[2 * p + j] = st[j];
+    }
+  }
+  if (st[0]) report_error(err, 2 * p, st[0]);
+  if (two && st[1]) report_error(err, 2 * p + 1, st[1]);
+}
+
 template <int PERIOD, bool LENIENT, bool F32, bool VEC>
 __global__ __launch_bounds__(ATPB) void k_z3_key_arrow(ArrowPts g, ArrowTime tc, int64_t n, NDim lon, NDim lat,
                                                        NDim tim, int16_t* __restrict__ bin, int64_t* __restrict__ z,
                                                        uint8_t* __restrict__ status, int64_t* __restrict__ err) {
-  const int64_t npairs = (n + 1) >> 1;
-  for (int64_t p = (int64_t)blockIdx.x * ATPB + threadIdx.x; p < npairs; p += (int64_t)gridDim.x * ATPB) {
+  row_stream<ATPB>((n + 1) >> 1, [&](int64_t p) {
     const bool two = 2 * p + 1 < n;
     int16_t b[2] = {0, 0};
     int64_t zz[2] = {0, 0};
     uint8_t st[2] = {ST_OK, ST_OK};
-    int64_t tt[2];
-    if (two) arrow_time_pair(tc, p, VEC, tt[0], tt[1]);
-    else { tt[0] = arrow_time(tc, 2 * p); tt[1] = 0; }
+    int64_t t0, t1 = 0;
+    if (two) arrow_time_pair(tc, p, VEC, t0, t1);
+    else t0 = arrow_time(tc, 2 * p);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int64_t i = 2 * p + j;
@@ -66,20 +88,10 @@ __global__ __launch_bounds__(ATPB) void k_z3_key_arrow(ArrowPts g, ArrowTime tc,
       if (!arrow_valid(g.valid, g.voff, i)) { st[j] = ST_NULL_GEOM; continue; }
       double x, y;
       arrow_tuple<F32>(g.c, i, g.flip, x, y);
-      st[j] = z3_key_one<PERIOD, LENIENT>(x, y, tt[j], lon, lat, tim, b[j], zz[j]);
+      st[j] = z3_key_one<PERIOD, LENIENT>(x, y, j ? t1 : t0, lon, lat, tim, b[j], zz[j]);
     }
-    if (VEC && two) {
-      st_stream(lv2{zz[0], zz[1]}, &((lv2*)z)[p]);
-      ((short2*)bin)[p] = make_short2(b[0], b[1]);
-      if (status) ((uchar2*)status)[p] = make_uchar2(st[0], st[1]);
-    } else {
-      z[2 * p] = zz[0]; bin[2 * p] = b[0];
-      if (status) status[2 * p] = st[0];
-      if (two) { z[2 * p + 1] = zz[1]; bin[2 * p + 1] = b[1]; if (status) status[2 * p + 1] = st[1]; }
-    }
-    if (st[0]) report_error(err, 2 * p, st[0]);
-    if (two && st[1]) report_error(err, 2 * p + 1, st[1]);
-  }
+    store_two_rows(VEC, two, p, zz, b, st, z, bin, status, err);
+  });
 }
 
 // the aligned, full-pair form of k_z3_key_arrow: one chunk of ATPB * UNROLL pairs per workgroup, every
@@ -104,6 +116,8 @@ __global__ __launch_bounds__(ATPB) void k_z3_key_arrow_v(ArrowPts g, ArrowTime t
                                                          uchar2* __restrict__ status, int64_t* __restrict__ err) {
   static_assert(UNROLL == 4, "staged bins: 4 pairs per lane");
   __shared__ uint32_t s_bin[ATPB * UNROLL];   // the block's bins, stored 16 B per lane at the end
+  // pair_stream's shape with the full-block branch, written out: on the skeleton this kernel lost its A/B in
+  // two visits (profiles/stream_skeleton_ab.txt)
   const int64_t npairs = n >> 1;
   const int64_t base = (int64_t)blockIdx.x * (ATPB * UNROLL) + threadIdx.x;
   dv2 a[UNROLL], b[UNROLL];
@@ -171,8 +185,7 @@ template <bool LENIENT, bool F32, bool VEC>
 __global__ __launch_bounds__(ATPB) void k_z2_key_arrow(ArrowPts g, int64_t n, NDim lon, NDim lat,
                                                        int64_t* __restrict__ z, uint8_t* __restrict__ status,
                                                        int64_t* __restrict__ err) {
-  const int64_t npairs = (n + 1) >> 1;
-  for (int64_t p = (int64_t)blockIdx.x * ATPB + threadIdx.x; p < npairs; p += (int64_t)gridDim.x * ATPB) {
+  row_stream<ATPB>((n + 1) >> 1, [&](int64_t p) {
     const bool two = 2 * p + 1 < n;
     int64_t zz[2] = {0, 0};
     uint8_t st[2] = {ST_OK, ST_OK};
@@ -185,35 +198,26 @@ __global__ __launch_bounds__(ATPB) void k_z2_key_arrow(ArrowPts g, int64_t n, ND
       arrow_tuple<F32>(g.c, i, g.flip, x, y);
       st[j] = z2_index_one<LENIENT>(x, y, lon, lat, zz[j]);
     }
-    if (VEC && two) {
-      st_stream(lv2{zz[0], zz[1]}, &((lv2*)z)[p]);
-      if (status) ((uchar2*)status)[p] = make_uchar2(st[0], st[1]);
-    } else {
-      z[2 * p] = zz[0];
-      if (status) status[2 * p] = st[0];
-      if (two) { z[2 * p + 1] = zz[1]; if (status) status[2 * p + 1] = st[1]; }
-    }
-    if (st[0]) report_error(err, 2 * p, st[0]);
-    if (two && st[1]) report_error(err, 2 * p + 1, st[1]);
-  }
+    store_two_rows(VEC, two, p, zz, nullptr, st, z, nullptr, status, err);
+  });
 }
 
 template <bool F32>
 __global__ __launch_bounds__(ATPB) void k_points_soa(ArrowPts g, int64_t n, double* __restrict__ x,
                                                      double* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * ATPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * ATPB) {
+  row_stream<ATPB>(n, [&](int64_t i) {
     double px = NAN, py = NAN;
     if (arrow_valid(g.valid, g.voff, i)) arrow_tuple<F32>(g.c, i, g.flip, px, py);
     x[i] = px;
     y[i] = py;
-  }
+  });
 }
 
 // the adapter over a GM_GEOM_WKB column: x, y of a slot whose top-level geometry is a Point; a null or
 // malformed slot, the empty point (a NaN ordinate) and every other class are NaN, NaN
 __global__ __launch_bounds__(ATPB) void k_points_soa_wkb(ArrowGeom g, int64_t n, double* __restrict__ x,
                                                          double* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * ATPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * ATPB) {
+  row_stream<ATPB>(n, [&](int64_t i) {
     double px = NAN, py = NAN;
     if (arrow_valid(g.valid, g.voff, i)) {
       WkbCur c = wkb_slot(g, i);
@@ -226,7 +230,7 @@ __global__ __launch_bounds__(ATPB) void k_points_soa_wkb(ArrowGeom g, int64_t n,
     }
     x[i] = px;
     y[i] = py;
-  }
+  });
 }
 
 // ------------------------------------------------------------------ envelopes (XZ keys)
@@ -239,7 +243,7 @@ __global__ __launch_bounds__(ATPB) void k_xz_key_arrow(ArrowGeom g, ArrowTime tc
                                                        int16_t* __restrict__ bin, int64_t* __restrict__ xz,
                                                        uint8_t* __restrict__ status, int64_t* __restrict__ err) {
   __shared__ uint32_t s_rem[WKB ? WKB_DEPTH * ATPB : 1];   // wkb_walk's stack, one column per lane
-  for (int64_t i = (int64_t)blockIdx.x * ATPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * ATPB) {
+  row_stream<ATPB>(n, [&](int64_t i) {
     int64_t out = 0;
     int16_t b = 0;
     uint8_t st;
@@ -262,18 +266,13 @@ __global__ __launch_bounds__(ATPB) void k_xz_key_arrow(ArrowGeom g, ArrowTime tc
     if (st != ST_OK) out = 0;
     xz[i] = out;
     if (DIM == 3) bin[i] = b;
-    if (status) status[i] = st;
-    if (st) report_error(err, i, st);
-  }
+    finish_row(status != nullptr, status, err, i, st);
+  });
 }
 
 // ------------------------------------------------------------------ host side
 
-inline unsigned agrid(int64_t units) {
-  int64_t b = (units + ATPB - 1) / ATPB;
-  if (b > 256 * 32) b = 256 * 32;
-  return (unsigned)(b < 1 ? 1 : b);
-}
+inline unsigned agrid(int64_t units) { return stride_grid(units, ATPB, 256 * 32); }
 
 inline bool point_col_ok(const gm_geom_column* g) {
   return g && g->type == GM_GEOM_POINT && (g->ordinal_bits == 64 || g->ordinal_bits == 32) && g->coords;
@@ -293,11 +292,10 @@ template <int PERIOD, bool LENIENT, bool F32>
 void launch_z3_arrow(hipStream_t s, bool vec, ArrowPts g, ArrowTime tc, int64_t n, NDim lon, NDim lat, NDim tim,
                      int16_t* bin, int64_t* z, uint8_t* status, int64_t* err) {
   if (vec && aligned16(g.c) && n >= 2) {
-    const int64_t np = n >> 1;
-    const unsigned vg = (unsigned)((np + ATPB * AUNROLL - 1) / (ATPB * AUNROLL));
     with_flags([&](auto T) {
-      hipLaunchKernelGGL((k_z3_key_arrow_v<PERIOD, LENIENT, F32, T(), AUNROLL>), dim3(vg), dim3(ATPB), 0, s, g, tc, n,
-                         lon, lat, tim, (short2*)bin, (lv2*)z, (uchar2*)status, err);
+      hipLaunchKernelGGL((k_z3_key_arrow_v<PERIOD, LENIENT, F32, T(), AUNROLL>),
+                         dim3(pair_grid(n, (int64_t)ATPB * AUNROLL)), dim3(ATPB), 0, s, g, tc, n, lon, lat, tim,
+                         (short2*)bin, (lv2*)z, (uchar2*)status, err);
     }, tc.ms != nullptr);
     return;
   }

@@ -1,11 +1,17 @@
 // gm_curve.hip -- Z3/Z2 encode+decode, BinnedTime and XZ2/XZ3 envelope keys on gfx950.
 //
 // All of these are HBM-streaming element-wise kernels (34 B/point for the Z3 key, 32 B for the Z3
-// invert, 24 B for Z2, 40/56 B for XZ): no reuse, no LDS, no MFMA.  Shape: 256-thread workgroups,
-// each lane moves 2 consecutive elements with 16-byte loads/stores (one dwordx4 per column per
-// lane), UNROLL independent pairs in flight per lane, fully coalesced per wave instruction
-// (pair p of lane l in step u sits at block_base + u*256 + l).  One chunk per workgroup -- the
-// grid is large (N / 2048 workgroups at UNROLL = 4), so all 256 CUs x 8 XCDs fill.
+// invert, 24 B for Z2, 40/56 B for XZ): no reuse, no MFMA.  Each kernel is a per-element body from
+// gm_keys.hpp inside one of gm_stream.hpp's two loops:
+//   pair_stream  the 16-B form, taken when every column is 16-B aligned: a lane moves 2 consecutive
+//                elements per column with one dwordx4, UNROLL pairs in flight, one chunk of
+//                TPB * UNROLL pairs per workgroup -- the grid is large (N / 2048 workgroups at
+//                UNROLL = 4), so all 256 CUs x 8 XCDs fill;
+//   row_stream   a lane per element, grid-stride on a clamped grid: the fallbacks for unaligned columns
+//                (the _s kernels, k_xz2_index, k_xz3_index) and the entry points that have no pair form.
+// A kernel lists its loads, its pair body and its odd-row tail; block size, UNROLL and the store kind
+// stay per kernel (the sweeps quoted beside the GM_UNROLL_* macros).  k_z3_index_key has the pair shape
+// written out (it measured slower on pair_stream).
 #include "gm_keys.hpp"
 
 namespace gm {
@@ -32,6 +38,8 @@ __global__ __launch_bounds__(TPB) void k_z3_index_key(const dv2* __restrict__ x,
   // 4-B store per pair (A/B on one box, round 2)
   __shared__ uint32_t s_bin[TPB * UNROLL];
   static_assert(UNROLL == 4, "staged bins: 4 pairs per lane");
+  // pair_stream's shape written out: on the skeleton this kernel (and k_z3_key_arrow_v, gm_arrow.hip) lost
+  // its A/B in two visits (profiles/stream_skeleton_ab.txt), so both keep their own loops
   const int64_t npairs = n >> 1;
   const int64_t base = (int64_t)blockIdx.x * (TPB * UNROLL) + threadIdx.x;
   dv2 xv[UNROLL], yv[UNROLL];
@@ -81,15 +89,14 @@ __global__ __launch_bounds__(TPB) void k_z3_index_key_s(const double* __restrict
                                                         int16_t* __restrict__ bin, int64_t* __restrict__ z,
                                                         uint8_t* __restrict__ status, NDim lon, NDim lat, NDim tim,
                                                         int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+  row_stream<TPB>(n, [&](int64_t i) {
     int16_t b;
     int64_t zz;
-    uint8_t s = z3_key_one<PERIOD, LENIENT>(x[i], y[i], t[i], lon, lat, tim, b, zz);
+    const uint8_t s = z3_key_one<PERIOD, LENIENT>(x[i], y[i], t[i], lon, lat, tim, b, zz);
     bin[i] = b;
     z[i] = zz;
-    if (STATUS) status[i] = s;
-    if (s) report_error(err, i, s);
-  }
+    finish_row(STATUS, status, err, i, s);
+  });
 }
 
 // ------------------------------------------------------------------ Z3SFC.index (offset t)
@@ -99,13 +106,12 @@ __global__ __launch_bounds__(TPB) void k_z3_index(const double* __restrict__ x, 
                                                   const int64_t* __restrict__ t, int64_t n, int64_t* __restrict__ z,
                                                   uint8_t* __restrict__ status, NDim lon, NDim lat, NDim tim,
                                                   int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+  row_stream<TPB>(n, [&](int64_t i) {
     int64_t zz;
-    uint8_t s = z3_index_one<LENIENT>(x[i], y[i], t[i], lon, lat, tim, zz);
+    const uint8_t s = z3_index_one<LENIENT>(x[i], y[i], t[i], lon, lat, tim, zz);
     z[i] = zz;
-    if (STATUS) status[i] = s;
-    if (s) report_error(err, i, s);
-  }
+    finish_row(STATUS, status, err, i, s);
+  });
 }
 
 // ------------------------------------------------------------------ Z3SFC.invert
@@ -118,43 +124,25 @@ template <int UNROLL>
 __global__ __launch_bounds__(TPB) void k_z3_invert(const lv2* __restrict__ z, int64_t n, dv2* __restrict__ x,
                                                    dv2* __restrict__ y, lv2* __restrict__ t, NDim lon,
                                                    NDim lat, NDim tim) {
-  const int64_t npairs = n >> 1;
-  const int64_t base = (int64_t)blockIdx.x * (TPB * UNROLL) + threadIdx.x;
   lv2 zv[UNROLL];
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * TPB;
-    if (p < npairs) zv[u] = ld_stream(&z[p]);
-  }
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * TPB;
-    if (p < npairs) {
-      const int64_t a = zv[u].x, b = zv[u].y;
-      const dv2 xo{denormalize(lon, z3_combine(a)), denormalize(lon, z3_combine(b))};
-      const dv2 yo{denormalize(lat, z3_combine(a >> 1)), denormalize(lat, z3_combine(b >> 1))};
-      const lv2 to{jvm_d2l(denormalize(tim, z3_combine(a >> 2))), jvm_d2l(denormalize(tim, z3_combine(b >> 2)))};
-      x[p] = xo; y[p] = yo; t[p] = to;
-    }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    const int64_t a = ((const int64_t*)z)[i];
-    ((double*)x)[i] = denormalize(lon, z3_combine(a));
-    ((double*)y)[i] = denormalize(lat, z3_combine(a >> 1));
-    ((int64_t*)t)[i] = jvm_d2l(denormalize(tim, z3_combine(a >> 2)));
-  }
+  pair_stream<TPB, UNROLL>(
+      n, [&](int u, int64_t p) { zv[u] = ld_stream(&z[p]); },
+      [&](int u, int64_t p) {
+        double x0, y0, x1, y1;
+        int64_t t0, t1;
+        z3_invert_one(zv[u].x, lon, lat, tim, x0, y0, t0);
+        z3_invert_one(zv[u].y, lon, lat, tim, x1, y1, t1);
+        x[p] = dv2{x0, x1}; y[p] = dv2{y0, y1}; t[p] = lv2{t0, t1};
+      },
+      [&](int64_t i) {
+        z3_invert_one(((const int64_t*)z)[i], lon, lat, tim, ((double*)x)[i], ((double*)y)[i], ((int64_t*)t)[i]);
+      });
 }
 
 __global__ __launch_bounds__(TPB) void k_z3_invert_s(const int64_t* __restrict__ z, int64_t n, double* __restrict__ x,
                                                      double* __restrict__ y, int64_t* __restrict__ t, NDim lon,
                                                      NDim lat, NDim tim) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int64_t a = z[i];
-    x[i] = denormalize(lon, z3_combine(a));
-    y[i] = denormalize(lat, z3_combine(a >> 1));
-    t[i] = jvm_d2l(denormalize(tim, z3_combine(a >> 2)));
-  }
+  row_stream<TPB>(n, [&](int64_t i) { z3_invert_one(z[i], lon, lat, tim, x[i], y[i], t[i]); });
 }
 
 // ------------------------------------------------------------------ Z2SFC.index / invert
@@ -163,90 +151,59 @@ template <bool LENIENT, bool STATUS, int UNROLL>
 __global__ __launch_bounds__(TPB) void k_z2_index(const dv2* __restrict__ x, const dv2* __restrict__ y,
                                                   int64_t n, lv2* __restrict__ z, uchar2* __restrict__ status,
                                                   NDim lon, NDim lat, int64_t* __restrict__ err) {
-  const int64_t npairs = n >> 1;
-  const int64_t base = (int64_t)blockIdx.x * (TPB * UNROLL) + threadIdx.x;
   dv2 xv[UNROLL], yv[UNROLL];
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * TPB;
-    if (p < npairs) {
-      xv[u] = ld_stream(&x[p]);
-      yv[u] = ld_stream(&y[p]);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * TPB;
-    if (p < npairs) {
-      int64_t z0, z1;
-      uint8_t s0 = z2_index_one<LENIENT>(xv[u].x, yv[u].x, lon, lat, z0);
-      uint8_t s1 = z2_index_one<LENIENT>(xv[u].y, yv[u].y, lon, lat, z1);
-      st_stream(lv2{z0, z1}, &z[p]);
-      if (STATUS) status[p] = make_uchar2(s0, s1);
-      if (s0) report_error(err, 2 * p, s0);
-      if (s1) report_error(err, 2 * p + 1, s1);
-    }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    int64_t zz;
-    uint8_t s = z2_index_one<LENIENT>(((const double*)x)[i], ((const double*)y)[i], lon, lat, zz);
-    ((int64_t*)z)[i] = zz;
-    if (STATUS) ((uint8_t*)status)[i] = s;
-    if (s) report_error(err, i, s);
-  }
+  pair_stream<TPB, UNROLL>(
+      n,
+      [&](int u, int64_t p) {
+        xv[u] = ld_stream(&x[p]);
+        yv[u] = ld_stream(&y[p]);
+      },
+      [&](int u, int64_t p) {
+        int64_t z0, z1;
+        const uint8_t s0 = z2_index_one<LENIENT>(xv[u].x, yv[u].x, lon, lat, z0);
+        const uint8_t s1 = z2_index_one<LENIENT>(xv[u].y, yv[u].y, lon, lat, z1);
+        st_stream(lv2{z0, z1}, &z[p]);
+        finish_pair(STATUS, status, err, p, s0, s1);
+      },
+      [&](int64_t i) {
+        int64_t zz;
+        const uint8_t s = z2_index_one<LENIENT>(((const double*)x)[i], ((const double*)y)[i], lon, lat, zz);
+        ((int64_t*)z)[i] = zz;
+        finish_row(STATUS, (uint8_t*)status, err, i, s);
+      });
 }
 
 template <bool LENIENT, bool STATUS>
 __global__ __launch_bounds__(TPB) void k_z2_index_s(const double* __restrict__ x, const double* __restrict__ y,
                                                     int64_t n, int64_t* __restrict__ z, uint8_t* __restrict__ status,
                                                     NDim lon, NDim lat, int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+  row_stream<TPB>(n, [&](int64_t i) {
     int64_t zz;
-    uint8_t s = z2_index_one<LENIENT>(x[i], y[i], lon, lat, zz);
+    const uint8_t s = z2_index_one<LENIENT>(x[i], y[i], lon, lat, zz);
     z[i] = zz;
-    if (STATUS) status[i] = s;
-    if (s) report_error(err, i, s);
-  }
+    finish_row(STATUS, status, err, i, s);
+  });
 }
 
 template <int UNROLL>
 __global__ __launch_bounds__(TPB) void k_z2_invert(const lv2* __restrict__ z, int64_t n, dv2* __restrict__ x,
                                                    dv2* __restrict__ y, NDim lon, NDim lat) {
-  const int64_t npairs = n >> 1;
-  const int64_t base = (int64_t)blockIdx.x * (TPB * UNROLL) + threadIdx.x;
   lv2 zv[UNROLL];
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * TPB;
-    if (p < npairs) zv[u] = ld_stream(&z[p]);
-  }
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * TPB;
-    if (p < npairs) {
-      const int64_t a = zv[u].x, b = zv[u].y;
-      st_stream(dv2{denormalize(lon, z2_combine(a)), denormalize(lon, z2_combine(b))},
-                                  &x[p]);
-      st_stream(
-          dv2{denormalize(lat, z2_combine(a >> 1)), denormalize(lat, z2_combine(b >> 1))}, &y[p]);
-    }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    const int64_t a = ((const int64_t*)z)[i];
-    ((double*)x)[i] = denormalize(lon, z2_combine(a));
-    ((double*)y)[i] = denormalize(lat, z2_combine(a >> 1));
-  }
+  pair_stream<TPB, UNROLL>(
+      n, [&](int u, int64_t p) { zv[u] = ld_stream(&z[p]); },
+      [&](int u, int64_t p) {
+        double x0, y0, x1, y1;
+        z2_invert_one(zv[u].x, lon, lat, x0, y0);
+        z2_invert_one(zv[u].y, lon, lat, x1, y1);
+        st_stream(dv2{x0, x1}, &x[p]);
+        st_stream(dv2{y0, y1}, &y[p]);
+      },
+      [&](int64_t i) { z2_invert_one(((const int64_t*)z)[i], lon, lat, ((double*)x)[i], ((double*)y)[i]); });
 }
 
 __global__ __launch_bounds__(TPB) void k_z2_invert_s(const int64_t* __restrict__ z, int64_t n, double* __restrict__ x,
                                                      double* __restrict__ y, NDim lon, NDim lat) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const int64_t a = z[i];
-    x[i] = denormalize(lon, z2_combine(a));
-    y[i] = denormalize(lat, z2_combine(a >> 1));
-  }
+  row_stream<TPB>(n, [&](int64_t i) { z2_invert_one(z[i], lon, lat, x[i], y[i]); });
 }
 
 // ------------------------------------------------------------------ BinnedTime
@@ -255,29 +212,29 @@ template <int PERIOD, bool STATUS>
 __global__ __launch_bounds__(TPB) void k_binned_time(const int64_t* __restrict__ t, int64_t n,
                                                      int16_t* __restrict__ bin, int64_t* __restrict__ off,
                                                      uint8_t* __restrict__ status, int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+  row_stream<TPB>(n, [&](int64_t i) {
     int16_t b;
     int64_t o;
-    uint8_t s = binned_time<PERIOD>(t[i], b, o);
+    const uint8_t s = binned_time<PERIOD>(t[i], b, o);
     bin[i] = b;
     off[i] = o;
-    if (STATUS) status[i] = s;
-    if (s) report_error(err, i, s);
-  }
+    finish_row(STATUS, status, err, i, s);
+  });
 }
+
+// ------------------------------------------------------------------ XZ2 / XZ3
 
 template <bool LENIENT, bool STATUS>
 __global__ __launch_bounds__(TPB) void k_xz2_index(const double* __restrict__ xmin, const double* __restrict__ ymin,
                                                    const double* __restrict__ xmax, const double* __restrict__ ymax,
                                                    int64_t n, int g, int64_t* __restrict__ out,
                                                    uint8_t* __restrict__ status, int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+  row_stream<TPB>(n, [&](int64_t i) {
     int64_t o;
-    uint8_t s = xz2_one<LENIENT>(g, xmin[i], ymin[i], xmax[i], ymax[i], o);
+    const uint8_t s = xz2_one<LENIENT>(g, xmin[i], ymin[i], xmax[i], ymax[i], o);
     out[i] = o;
-    if (STATUS) status[i] = s;
-    if (s) report_error(err, i, s);
-  }
+    finish_row(STATUS, status, err, i, s);
+  });
 }
 
 template <bool LENIENT, bool STATUS>
@@ -286,13 +243,12 @@ __global__ __launch_bounds__(TPB) void k_xz3_index(const double* __restrict__ xm
                                                    const double* __restrict__ ymax, const double* __restrict__ zmax,
                                                    int64_t n, int g, double zhi, int64_t* __restrict__ out,
                                                    uint8_t* __restrict__ status, int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+  row_stream<TPB>(n, [&](int64_t i) {
     int64_t o;
-    uint8_t s = xz3_one<LENIENT>(g, zhi, xmin[i], ymin[i], zmin[i], xmax[i], ymax[i], zmax[i], o);
+    const uint8_t s = xz3_one<LENIENT>(g, zhi, xmin[i], ymin[i], zmin[i], xmax[i], ymax[i], zmax[i], o);
     out[i] = o;
-    if (STATUS) status[i] = s;
-    if (s) report_error(err, i, s);
-  }
+    finish_row(STATUS, status, err, i, s);
+  });
 }
 
 // XZ3IndexKeySpace.toIndexKey (idx/index/z3/XZ3IndexKeySpace.scala:60-95) over envelope + dtg columns:
@@ -304,7 +260,7 @@ __global__ __launch_bounds__(TPB) void k_xz3_index_key(const double* __restrict_
                                                        const int64_t* __restrict__ t_ms, int64_t n, int g, double zhi,
                                                        int16_t* __restrict__ bin, int64_t* __restrict__ out,
                                                        uint8_t* __restrict__ status, int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+  row_stream<TPB>(n, [&](int64_t i) {
     int64_t o = 0, off = 0;
     int16_t b = 0;
     uint8_t s = binned_time<PERIOD>(t_ms ? t_ms[i] : 0, b, off);
@@ -315,51 +271,37 @@ __global__ __launch_bounds__(TPB) void k_xz3_index_key(const double* __restrict_
     if (s != ST_OK) { o = 0; b = 0; }
     out[i] = o;
     bin[i] = b;
-    if (STATUS) status[i] = s;
-    if (s) report_error(err, i, s);
-  }
+    finish_row(STATUS, status, err, i, s);
+  });
 }
 
-// 16-B form: 2 envelopes per lane per column (one dwordx4 each), UNROLL pairs in flight per lane,
-// the same coalesced layout as the Z3 key kernel; the odd last envelope goes to lane 0 of block 0.
+// 16-B form: 2 envelopes per lane per column (one dwordx4 each), the Z3 key kernel's layout
 template <bool LENIENT, bool STATUS, int UNROLL>
 __global__ __launch_bounds__(XTPB) void k_xz2_index_v(const dv2* __restrict__ xmin, const dv2* __restrict__ ymin,
                                                      const dv2* __restrict__ xmax, const dv2* __restrict__ ymax,
                                                      int64_t n, int g, lv2* __restrict__ out,
                                                      uchar2* __restrict__ status, int64_t* __restrict__ err) {
-  const int64_t npairs = n >> 1;
-  const int64_t base = (int64_t)blockIdx.x * (XTPB * UNROLL) + threadIdx.x;
   dv2 a[UNROLL], b[UNROLL], c[UNROLL], d[UNROLL];
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * XTPB;
-    if (p < npairs) {
-      a[u] = ld_stream(&xmin[p]); b[u] = ld_stream(&ymin[p]);
-      c[u] = ld_stream(&xmax[p]); d[u] = ld_stream(&ymax[p]);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * XTPB;
-    if (p < npairs) {
-      int64_t o0, o1;
-      const uint8_t s0 = xz2_one<LENIENT>(g, a[u].x, b[u].x, c[u].x, d[u].x, o0);
-      const uint8_t s1 = xz2_one<LENIENT>(g, a[u].y, b[u].y, c[u].y, d[u].y, o1);
-      st_stream(lv2{o0, o1}, &out[p]);
-      if (STATUS) status[p] = make_uchar2(s0, s1);
-      if (s0) report_error(err, 2 * p, s0);
-      if (s1) report_error(err, 2 * p + 1, s1);
-    }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    int64_t o;
-    const uint8_t s = xz2_one<LENIENT>(g, ((const double*)xmin)[i], ((const double*)ymin)[i],
-                                       ((const double*)xmax)[i], ((const double*)ymax)[i], o);
-    ((int64_t*)out)[i] = o;
-    if (STATUS) ((uint8_t*)status)[i] = s;
-    if (s) report_error(err, i, s);
-  }
+  pair_stream<XTPB, UNROLL>(
+      n,
+      [&](int u, int64_t p) {
+        a[u] = ld_stream(&xmin[p]); b[u] = ld_stream(&ymin[p]);
+        c[u] = ld_stream(&xmax[p]); d[u] = ld_stream(&ymax[p]);
+      },
+      [&](int u, int64_t p) {
+        int64_t o0, o1;
+        const uint8_t s0 = xz2_one<LENIENT>(g, a[u].x, b[u].x, c[u].x, d[u].x, o0);
+        const uint8_t s1 = xz2_one<LENIENT>(g, a[u].y, b[u].y, c[u].y, d[u].y, o1);
+        st_stream(lv2{o0, o1}, &out[p]);
+        finish_pair(STATUS, status, err, p, s0, s1);
+      },
+      [&](int64_t i) {
+        int64_t o;
+        const uint8_t s = xz2_one<LENIENT>(g, ((const double*)xmin)[i], ((const double*)ymin)[i],
+                                           ((const double*)xmax)[i], ((const double*)ymax)[i], o);
+        ((int64_t*)out)[i] = o;
+        finish_row(STATUS, (uint8_t*)status, err, i, s);
+      });
 }
 
 template <bool LENIENT, bool STATUS, int UNROLL>
@@ -368,40 +310,28 @@ __global__ __launch_bounds__(XTPB) void k_xz3_index_v(const dv2* __restrict__ xm
                                                      const dv2* __restrict__ ymax, const dv2* __restrict__ zmax,
                                                      int64_t n, int g, double zhi, lv2* __restrict__ out,
                                                      uchar2* __restrict__ status, int64_t* __restrict__ err) {
-  const int64_t npairs = n >> 1;
-  const int64_t base = (int64_t)blockIdx.x * (XTPB * UNROLL) + threadIdx.x;
   dv2 a[UNROLL], b[UNROLL], c[UNROLL], d[UNROLL], e[UNROLL], f[UNROLL];
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * XTPB;
-    if (p < npairs) {
-      a[u] = ld_stream(&xmin[p]); b[u] = ld_stream(&ymin[p]); c[u] = ld_stream(&zmin[p]);
-      d[u] = ld_stream(&xmax[p]); e[u] = ld_stream(&ymax[p]); f[u] = ld_stream(&zmax[p]);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
-    const int64_t p = base + (int64_t)u * XTPB;
-    if (p < npairs) {
-      int64_t o0, o1;
-      const uint8_t s0 = xz3_one<LENIENT>(g, zhi, a[u].x, b[u].x, c[u].x, d[u].x, e[u].x, f[u].x, o0);
-      const uint8_t s1 = xz3_one<LENIENT>(g, zhi, a[u].y, b[u].y, c[u].y, d[u].y, e[u].y, f[u].y, o1);
-      st_stream(lv2{o0, o1}, &out[p]);
-      if (STATUS) status[p] = make_uchar2(s0, s1);
-      if (s0) report_error(err, 2 * p, s0);
-      if (s1) report_error(err, 2 * p + 1, s1);
-    }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    int64_t o;
-    const uint8_t s = xz3_one<LENIENT>(g, zhi, ((const double*)xmin)[i], ((const double*)ymin)[i],
-                                       ((const double*)zmin)[i], ((const double*)xmax)[i], ((const double*)ymax)[i],
-                                       ((const double*)zmax)[i], o);
-    ((int64_t*)out)[i] = o;
-    if (STATUS) ((uint8_t*)status)[i] = s;
-    if (s) report_error(err, i, s);
-  }
+  pair_stream<XTPB, UNROLL>(
+      n,
+      [&](int u, int64_t p) {
+        a[u] = ld_stream(&xmin[p]); b[u] = ld_stream(&ymin[p]); c[u] = ld_stream(&zmin[p]);
+        d[u] = ld_stream(&xmax[p]); e[u] = ld_stream(&ymax[p]); f[u] = ld_stream(&zmax[p]);
+      },
+      [&](int u, int64_t p) {
+        int64_t o0, o1;
+        const uint8_t s0 = xz3_one<LENIENT>(g, zhi, a[u].x, b[u].x, c[u].x, d[u].x, e[u].x, f[u].x, o0);
+        const uint8_t s1 = xz3_one<LENIENT>(g, zhi, a[u].y, b[u].y, c[u].y, d[u].y, e[u].y, f[u].y, o1);
+        st_stream(lv2{o0, o1}, &out[p]);
+        finish_pair(STATUS, status, err, p, s0, s1);
+      },
+      [&](int64_t i) {
+        int64_t o;
+        const uint8_t s = xz3_one<LENIENT>(g, zhi, ((const double*)xmin)[i], ((const double*)ymin)[i],
+                                           ((const double*)zmin)[i], ((const double*)xmax)[i],
+                                           ((const double*)ymax)[i], ((const double*)zmax)[i], o);
+        ((int64_t*)out)[i] = o;
+        finish_row(STATUS, (uint8_t*)status, err, i, s);
+      });
 }
 
 // ------------------------------------------------------------------ host-side launchers
@@ -430,23 +360,15 @@ constexpr int UNROLL_XZ = GM_UNROLL_XZ;
 #endif
 constexpr int UNROLL_Z2 = GM_UNROLL_Z2;
 
-inline unsigned stride_grid(int64_t n) {
-  int64_t b = (n + TPB - 1) / TPB;
-  if (b > 256 * 16) b = 256 * 16;
-  return (unsigned)(b < 1 ? 1 : b);
-}
+inline dim3 rows_grid(int64_t n) { return dim3(stride_grid(n, TPB, 256 * 16)); }
 
-template <int PERIOD, bool LENIENT, bool STATUS>
-void launch_key(hipStream_t s, const double* x, const double* y, const int64_t* t, int64_t n, int16_t* bin,
-                int64_t* z, uint8_t* status, NDim lon, NDim lat, NDim tim, int64_t* err, bool vec) {
-  if (vec) {
-    hipLaunchKernelGGL((k_z3_index_key<PERIOD, LENIENT, STATUS, UNROLL_KEY>),
-                       dim3(pair_grid(n, (int64_t)TPB * UNROLL_KEY)), dim3(TPB), 0, s, (const dv2*)x, (const dv2*)y,
-                       (const lv2*)t, n, (short2*)bin, (lv2*)z, (uchar2*)status, lon, lat, tim, err);
-  } else {
-    hipLaunchKernelGGL((k_z3_index_key_s<PERIOD, LENIENT, STATUS>), dim3(stride_grid(n)), dim3(TPB), 0, s, x, y, t,
-                       n, bin, z, status, lon, lat, tim, err);
-  }
+// An entry point with both forms: every pointer aligned for the pair kernel (`vec`) -> `kv`, VTPB x UNROLL
+// pairs per block on pair_grid; else the row kernel `ks` on rows_grid.  The arguments are given once, as
+// the row kernel takes them, and cast to the pair kernel's pointer types.
+template <int VTPB, int UNROLL, class... KV, class... KS, class... A>
+void launch_pair_or_rows(hipStream_t s, bool vec, int64_t n, void (*kv)(KV...), void (*ks)(KS...), A... a) {
+  if (vec) hipLaunchKernelGGL(kv, dim3(pair_grid(n, (int64_t)VTPB * UNROLL)), dim3(VTPB), 0, s, (KV)a...);
+  else hipLaunchKernelGGL(ks, rows_grid(n), dim3(TPB), 0, s, (KS)a...);
 }
 
 }  // namespace gm
@@ -467,7 +389,9 @@ int gm_z3_index_key(gm_ctx* ctx, const double* x, const double* y, const int64_t
                    aligned_to<2>(status);
   with_period(period, [&](auto P) {
     with_flags([&](auto L, auto S) {
-      launch_key<P(), L(), S()>(ctx->stream, x, y, t_ms, n, bin, z, status, lon, lat, tim, ctx->d_err, vec);
+      launch_pair_or_rows<TPB, UNROLL_KEY>(ctx->stream, vec, n, k_z3_index_key<P(), L(), S(), UNROLL_KEY>,
+                                           k_z3_index_key_s<P(), L(), S()>, x, y, t_ms, n, bin, z, status, lon, lat,
+                                           tim, ctx->d_err);
     }, lenient != 0, status != nullptr);
   });
   GM_CHECK_LAUNCH();
@@ -483,8 +407,8 @@ int gm_z3_index(gm_ctx* ctx, const double* x, const double* y, const int64_t* t,
   if (rc) return rc;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision), tim = time_dim(period, precision);
   with_flags([&](auto L, auto S) {
-    hipLaunchKernelGGL((k_z3_index<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status,
-                       lon, lat, tim, ctx->d_err);
+    hipLaunchKernelGGL((k_z3_index<L(), S()>), rows_grid(n), dim3(TPB), 0, ctx->stream, x, y, t, n, z, status, lon,
+                       lat, tim, ctx->d_err);
   }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
@@ -496,12 +420,9 @@ int gm_z3_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int period, int preci
   if (n == 0) return GM_OK;
   if (!z || !x || !y || !t) return GM_E_INVALID;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision), tim = time_dim(period, precision);
-  if (aligned16(z) && aligned16(x) && aligned16(y) && aligned16(t)) {
-    hipLaunchKernelGGL((k_z3_invert<UNROLL_INV>), dim3(pair_grid(n, (int64_t)TPB * UNROLL_INV)), dim3(TPB), 0,
-                       ctx->stream, (const lv2*)z, n, (dv2*)x, (dv2*)y, (lv2*)t, lon, lat, tim);
-  } else {
-    hipLaunchKernelGGL(k_z3_invert_s, dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, z, n, x, y, t, lon, lat, tim);
-  }
+  const bool vec = aligned16(z) && aligned16(x) && aligned16(y) && aligned16(t);
+  launch_pair_or_rows<TPB, UNROLL_INV>(ctx->stream, vec, n, k_z3_invert<UNROLL_INV>, k_z3_invert_s, z, n, x, y, t, lon,
+                                       lat, tim);
   GM_CHECK_LAUNCH();
   return GM_OK;
 }
@@ -515,17 +436,10 @@ int gm_z2_index(gm_ctx* ctx, const double* x, const double* y, int64_t n, int pr
   if (rc) return rc;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision);
   const bool vec = aligned16(x) && aligned16(y) && aligned16(z) && aligned_to<2>(status);
-  hipStream_t s = ctx->stream;
-  if (vec)
-    with_flags([&](auto L, auto S) {
-      hipLaunchKernelGGL((k_z2_index<L(), S(), UNROLL_Z2>), dim3(pair_grid(n, (int64_t)TPB * UNROLL_Z2)), dim3(TPB), 0,
-                         s, (const dv2*)x, (const dv2*)y, n, (lv2*)z, (uchar2*)status, lon, lat, ctx->d_err);
-    }, lenient != 0, status != nullptr);
-  else
-    with_flags([&](auto L, auto S) {
-      hipLaunchKernelGGL((k_z2_index_s<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, s, x, y, n, z, status, lon, lat,
-                         ctx->d_err);
-    }, lenient != 0, status != nullptr);
+  with_flags([&](auto L, auto S) {
+    launch_pair_or_rows<TPB, UNROLL_Z2>(ctx->stream, vec, n, k_z2_index<L(), S(), UNROLL_Z2>, k_z2_index_s<L(), S()>, x,
+                                        y, n, z, status, lon, lat, ctx->d_err);
+  }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -535,12 +449,9 @@ int gm_z2_invert(gm_ctx* ctx, const int64_t* z, int64_t n, int precision, double
   if (n == 0) return GM_OK;
   if (!z || !x || !y) return GM_E_INVALID;
   const NDim lon = lon_dim(precision), lat = lat_dim(precision);
-  if (aligned16(z) && aligned16(x) && aligned16(y)) {
-    hipLaunchKernelGGL((k_z2_invert<UNROLL_INV2>), dim3(pair_grid(n, (int64_t)TPB * UNROLL_INV2)), dim3(TPB), 0,
-                       ctx->stream, (const lv2*)z, n, (dv2*)x, (dv2*)y, lon, lat);
-  } else {
-    hipLaunchKernelGGL(k_z2_invert_s, dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, z, n, x, y, lon, lat);
-  }
+  const bool vec = aligned16(z) && aligned16(x) && aligned16(y);
+  launch_pair_or_rows<TPB, UNROLL_INV2>(ctx->stream, vec, n, k_z2_invert<UNROLL_INV2>, k_z2_invert_s, z, n, x, y, lon,
+                                        lat);
   GM_CHECK_LAUNCH();
   return GM_OK;
 }
@@ -554,8 +465,8 @@ int gm_binned_time(gm_ctx* ctx, const int64_t* t_ms, int64_t n, int period, int1
   if (rc) return rc;
   with_period(period, [&](auto P) {
     with_flags([&](auto S) {
-      hipLaunchKernelGGL((k_binned_time<P(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, t_ms, n, bin,
-                         offset, status, ctx->d_err);
+      hipLaunchKernelGGL((k_binned_time<P(), S()>), rows_grid(n), dim3(TPB), 0, ctx->stream, t_ms, n, bin, offset,
+                         status, ctx->d_err);
     }, status != nullptr);
   });
   GM_CHECK_LAUNCH();
@@ -569,20 +480,12 @@ int gm_xz2_index(gm_ctx* ctx, const double* xmin, const double* ymin, const doub
   if (!xmin || !ymin || !xmax || !ymax || !out) return GM_E_INVALID;
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
-  hipStream_t s = ctx->stream;
   const bool vec = aligned16(xmin) && aligned16(ymin) && aligned16(xmax) && aligned16(ymax) && aligned16(out) &&
                    aligned_to<2>(status);
-  if (vec)
-    with_flags([&](auto L, auto S) {
-      hipLaunchKernelGGL((k_xz2_index_v<L(), S(), UNROLL_XZ>), dim3(pair_grid(n, (int64_t)XTPB * UNROLL_XZ)),
-                         dim3(XTPB), 0, s, (const dv2*)xmin, (const dv2*)ymin, (const dv2*)xmax, (const dv2*)ymax, n, g,
-                         (lv2*)out, (uchar2*)status, ctx->d_err);
-    }, lenient != 0, status != nullptr);
-  else
-    with_flags([&](auto L, auto S) {
-      hipLaunchKernelGGL((k_xz2_index<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, s, xmin, ymin, xmax, ymax, n, g,
-                         out, status, ctx->d_err);
-    }, lenient != 0, status != nullptr);
+  with_flags([&](auto L, auto S) {
+    launch_pair_or_rows<XTPB, UNROLL_XZ>(ctx->stream, vec, n, k_xz2_index_v<L(), S(), UNROLL_XZ>, k_xz2_index<L(), S()>,
+                                         xmin, ymin, xmax, ymax, n, g, out, status, ctx->d_err);
+  }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -596,20 +499,12 @@ int gm_xz3_index(gm_ctx* ctx, const double* xmin, const double* ymin, const doub
   int rc = begin_summary(ctx, summary);
   if (rc) return rc;
   const double zhi = (double)max_offset(period);
-  hipStream_t s = ctx->stream;
   const bool vec = aligned16(xmin) && aligned16(ymin) && aligned16(zmin) && aligned16(xmax) && aligned16(ymax) &&
                    aligned16(zmax) && aligned16(out) && aligned_to<2>(status);
-  if (vec)
-    with_flags([&](auto L, auto S) {
-      hipLaunchKernelGGL((k_xz3_index_v<L(), S(), UNROLL_XZ>), dim3(pair_grid(n, (int64_t)XTPB * UNROLL_XZ)),
-                         dim3(XTPB), 0, s, (const dv2*)xmin, (const dv2*)ymin, (const dv2*)zmin, (const dv2*)xmax,
-                         (const dv2*)ymax, (const dv2*)zmax, n, g, zhi, (lv2*)out, (uchar2*)status, ctx->d_err);
-    }, lenient != 0, status != nullptr);
-  else
-    with_flags([&](auto L, auto S) {
-      hipLaunchKernelGGL((k_xz3_index<L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, s, xmin, ymin, zmin, xmax, ymax,
-                         zmax, n, g, zhi, out, status, ctx->d_err);
-    }, lenient != 0, status != nullptr);
+  with_flags([&](auto L, auto S) {
+    launch_pair_or_rows<XTPB, UNROLL_XZ>(ctx->stream, vec, n, k_xz3_index_v<L(), S(), UNROLL_XZ>, k_xz3_index<L(), S()>,
+                                         xmin, ymin, zmin, xmax, ymax, zmax, n, g, zhi, out, status, ctx->d_err);
+  }, lenient != 0, status != nullptr);
   GM_CHECK_LAUNCH();
   return end_summary(ctx, summary, status);
 }
@@ -625,8 +520,8 @@ int gm_xz3_index_key(gm_ctx* ctx, const double* xmin, const double* ymin, const 
   const double zhi = (double)max_offset(period);
   with_period(period, [&](auto P) {
     with_flags([&](auto L, auto S) {
-      hipLaunchKernelGGL((k_xz3_index_key<P(), L(), S()>), dim3(stride_grid(n)), dim3(TPB), 0, ctx->stream, xmin, ymin,
-                         xmax, ymax, t_ms, n, g, zhi, bin, xz, status, ctx->d_err);
+      hipLaunchKernelGGL((k_xz3_index_key<P(), L(), S()>), rows_grid(n), dim3(TPB), 0, ctx->stream, xmin, ymin, xmax,
+                         ymax, t_ms, n, g, zhi, bin, xz, status, ctx->d_err);
     }, lenient != 0, status != nullptr);
   });
   GM_CHECK_LAUNCH();

@@ -1,9 +1,10 @@
 // gm_keys.hpp -- per-element key bodies (Z3 / Z2 / XZ2 / XZ3 index with the JVM's bounds checks)
 // and the streaming load/store helpers, shared by the column kernels (gm_curve.hip) and the Arrow
-// kernels (gm_arrow.hip).
+// kernels (gm_arrow.hip).  The loops those bodies run in are gm_stream.hpp's.
 #pragma once
 
 #include "gm_internal.hpp"
+#include "gm_stream.hpp"
 
 namespace gm {
 
@@ -98,6 +99,18 @@ __device__ __forceinline__ uint8_t z2_index_one(double x, double y, const NDim& 
   }
   z = z2_apply(normalize(lon, x), normalize(lat, y));
   return ST_OK;
+}
+
+// Z3SFC.invert / Z2SFC.invert: the cell's centre per dimension, the time back as a Long
+__device__ __forceinline__ void z3_invert_one(int64_t z, const NDim& lon, const NDim& lat, const NDim& tim,
+                                              double& x, double& y, int64_t& t) {
+  x = denormalize(lon, z3_combine(z));
+  y = denormalize(lat, z3_combine(z >> 1));
+  t = jvm_d2l(denormalize(tim, z3_combine(z >> 2)));
+}
+__device__ __forceinline__ void z2_invert_one(int64_t z, const NDim& lon, const NDim& lat, double& x, double& y) {
+  x = denormalize(lon, z2_combine(z));
+  y = denormalize(lat, z2_combine(z >> 1));
 }
 
 // ------------------------------------------------------------------ XZ2 / XZ3

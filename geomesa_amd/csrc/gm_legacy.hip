@@ -1,6 +1,6 @@
 // gm_legacy.hip -- the deprecated curves GeoMesa keeps for reading and deleting old data:
 // LegacyZ3SFC (curve/LegacyZ3SFC.scala:18-49), LegacyZ2SFC (LegacyZ2SFC.scala:14-26) and
-// LegacyYearZ3SFC (LegacyYearZ3SFC.scala:17-46).  Same element-wise streaming shape as gm_curve.hip
+// LegacyYearZ3SFC (LegacyYearZ3SFC.scala:17-46).  A lane per element on row_stream (gm_stream.hpp)
 // (the legacy indices Z3IndexV4/V6 and Z2IndexV3 only ever call index / invert per feature).
 //
 // SemiNormalizedDimension (NormalizedDimension.scala:83-87):
@@ -30,67 +30,74 @@ __device__ __forceinline__ double semi_denormalize(const SemiDim& d, int32_t i) 
   return i == 0 ? d.min : (((double)i - 0.5) * (d.max - d.min)) / d.prec + d.min;
 }
 
+// LegacyZ3SFC.index / lenientIndex (LegacyZ3SFC.scala:18-28)
+__device__ __forceinline__ uint8_t legacy_z3_index_one(double x, double y, int64_t t, const SemiDim& lon,
+                                                       const SemiDim& lat, const SemiDim& tim, int lenient,
+                                                       int64_t& z) {
+  const double td = (double)t;
+  const bool inb = x >= lon.min && x <= lon.max && y >= lat.min && y <= lat.max && td >= tim.min && td <= tim.max;
+  z = 0;
+  if (inb) z = z3_apply(semi_normalize(lon, x), semi_normalize(lat, y), semi_normalize(tim, td));
+  else if (lenient) z = z3_apply(semi_lenient(lon, x), semi_lenient(lat, y), semi_lenient(tim, td));
+  else return ST_OUT_OF_BOUNDS;
+  return ST_OK;
+}
+
+// LegacyZ2SFC.index / lenientIndex (LegacyZ2SFC.scala:14-24)
+__device__ __forceinline__ uint8_t legacy_z2_index_one(double x, double y, const SemiDim& lon, const SemiDim& lat,
+                                                       int lenient, int64_t& z) {
+  const bool inb = x >= lon.min && x <= lon.max && y >= lat.min && y <= lat.max;
+  z = 0;
+  if (inb) z = z2_apply(semi_normalize(lon, x), semi_normalize(lat, y));
+  else if (lenient) z = z2_apply(semi_lenient(lon, x), semi_lenient(lat, y));
+  else return ST_OUT_OF_BOUNDS;
+  return ST_OK;
+}
+
 __global__ __launch_bounds__(LTPB) void k_legacy_z3_index(const double* __restrict__ x, const double* __restrict__ y,
                                                           const int64_t* __restrict__ t, int64_t n, SemiDim lon,
                                                           SemiDim lat, SemiDim tim, int lenient,
                                                           int64_t* __restrict__ z, uint8_t* __restrict__ status,
                                                           int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * LTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * LTPB) {
-    const double xx = x[i], yy = y[i], td = (double)t[i];
-    const bool inb = xx >= lon.min && xx <= lon.max && yy >= lat.min && yy <= lat.max && td >= tim.min &&
-                     td <= tim.max;
-    uint8_t st = ST_OK;
-    int64_t zz = 0;
-    if (inb) {
-      zz = z3_apply(semi_normalize(lon, xx), semi_normalize(lat, yy), semi_normalize(tim, td));
-    } else if (lenient) {  // LegacyZ3SFC.lenientIndex (LegacyZ3SFC.scala:23-28)
-      zz = z3_apply(semi_lenient(lon, xx), semi_lenient(lat, yy), semi_lenient(tim, td));
-    } else {
-      st = ST_OUT_OF_BOUNDS;
-    }
+  row_stream<LTPB>(n, [&](int64_t i) {
+    int64_t zz;
+    const uint8_t st = legacy_z3_index_one(x[i], y[i], t[i], lon, lat, tim, lenient, zz);
     z[i] = zz;
-    if (status) status[i] = st;
-    if (st) report_error(err, i, st);
-  }
+    finish_row(status != nullptr, status, err, i, st);
+  });
 }
 
 __global__ __launch_bounds__(LTPB) void k_legacy_z3_invert(const int64_t* __restrict__ z, int64_t n, SemiDim lon,
                                                            SemiDim lat, SemiDim tim, double* __restrict__ x,
                                                            double* __restrict__ y, int64_t* __restrict__ t) {
-  for (int64_t i = (int64_t)blockIdx.x * LTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * LTPB) {
+  row_stream<LTPB>(n, [&](int64_t i) {
     const int64_t zz = z[i];
     x[i] = semi_denormalize(lon, z3_combine(zz));
     y[i] = semi_denormalize(lat, z3_combine(zz >> 1));
     t[i] = jvm_d2l(semi_denormalize(tim, z3_combine(zz >> 2)));
-  }
+  });
 }
 
 __global__ __launch_bounds__(LTPB) void k_legacy_z2_index(const double* __restrict__ x, const double* __restrict__ y,
                                                           int64_t n, SemiDim lon, SemiDim lat, int lenient,
                                                           int64_t* __restrict__ z, uint8_t* __restrict__ status,
                                                           int64_t* __restrict__ err) {
-  for (int64_t i = (int64_t)blockIdx.x * LTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * LTPB) {
-    const double xx = x[i], yy = y[i];
-    const bool inb = xx >= lon.min && xx <= lon.max && yy >= lat.min && yy <= lat.max;
-    uint8_t st = ST_OK;
-    int64_t zz = 0;
-    if (inb) zz = z2_apply(semi_normalize(lon, xx), semi_normalize(lat, yy));
-    else if (lenient) zz = z2_apply(semi_lenient(lon, xx), semi_lenient(lat, yy));  // LegacyZ2SFC.scala:20-24
-    else st = ST_OUT_OF_BOUNDS;
+  row_stream<LTPB>(n, [&](int64_t i) {
+    int64_t zz;
+    const uint8_t st = legacy_z2_index_one(x[i], y[i], lon, lat, lenient, zz);
     z[i] = zz;
-    if (status) status[i] = st;
-    if (st) report_error(err, i, st);
-  }
+    finish_row(status != nullptr, status, err, i, st);
+  });
 }
 
 __global__ __launch_bounds__(LTPB) void k_legacy_z2_invert(const int64_t* __restrict__ z, int64_t n, SemiDim lon,
                                                            SemiDim lat, double* __restrict__ x,
                                                            double* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * LTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * LTPB) {
+  row_stream<LTPB>(n, [&](int64_t i) {
     const int64_t zz = z[i];
     x[i] = semi_denormalize(lon, z2_combine(zz));
     y[i] = semi_denormalize(lat, z2_combine(zz >> 1));
-  }
+  });
 }
 
 // LegacyYearZ3SFC.index (LegacyYearZ3SFC.scala:24-30): the standard 21-bit curve with the legacy
@@ -103,22 +110,17 @@ __global__ __launch_bounds__(LTPB) void k_legacy_year_z3_index(const double* __r
                                                                int64_t* __restrict__ z, uint8_t* __restrict__ status,
                                                                int64_t* __restrict__ err) {
   const int64_t tmax = (int64_t)tim.max;  // time.max.toLong
-  for (int64_t i = (int64_t)blockIdx.x * LTPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * LTPB) {
+  row_stream<LTPB>(n, [&](int64_t i) {
     int64_t tt = t[i];
     if ((double)tt > tim.max && tt <= year_max) tt = tmax;
     int64_t zz;
     const uint8_t st = z3_index_one<LENIENT>(x[i], y[i], tt, lon, lat, tim, zz);
     z[i] = zz;
-    if (status) status[i] = st;
-    if (st) report_error(err, i, st);
-  }
+    finish_row(status != nullptr, status, err, i, st);
+  });
 }
 
-inline unsigned legacy_grid(int64_t n) {
-  int64_t g = (n + LTPB - 1) / LTPB;
-  if (g > 256 * 32) g = 256 * 32;
-  return (unsigned)(g < 1 ? 1 : g);
-}
+inline unsigned legacy_grid(int64_t n) { return stride_grid(n, LTPB, 256 * 32); }
 
 inline SemiDim semi(double mn, double mx, int64_t prec) { return SemiDim{mn, mx, (double)prec}; }
 
