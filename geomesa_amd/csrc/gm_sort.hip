@@ -1,41 +1,28 @@
-// gm_sort.hip -- the sorted key table: row-key bytes, device sort into table order, and range scans.
+// gm_sort.hip -- gm_sort_keys: the key table's rows sorted on the device into table order.
 //
-// A GeoMesa Z3 table is the set of row keys [shard?][bin BE16][z BE64][id] kept in byte order by the
-// store (Z3IndexKeySpace.toIndexKey, idx/index/z3/Z3IndexKeySpace.scala:63-95; ByteArrays.writeShort /
-// writeLong, geomesa-utils/.../index/ByteArrays.scala:51,90-99).  A query seeks each byte range
-// getRangeBytes produces (Z3IndexKeySpace.scala:196-238) and the tablet server runs the Z3Filter on
-// every row inside (RowFilterIterator.scala:52-66).  Here the table is columnar and resident in HBM:
-//   * gm_z3_key_bytes  -- the row-key prefix bytes, staged through LDS so the stores are 16-B wide;
-//   * gm_sort_keys     -- a stable sort of (shard u8, bin u16, z u64) in that byte order.  The key
-//                         K = shard:bin:z is an 88-bit integer; one read finds its varying bits (OR /
-//                         AND), a second counts every pass's digits at once (k_sort_count).  Then
-//                         one-sweep digit passes (digits of <= 9 bits, k_sort_pass): 8192-row tiles
-//                         taken in order, ranked in LDS (wave ballots rank equal digits), each tile's
-//                         digit offsets found by a decoupled look-back over the tiles before it (8-B
-//                         {count, tag} granules), and the tile leaves as digit runs of 16-B records
-//                         {z, row, bs} (bs = bin | shard << sq, squeeze_bs).  The passes order the rows by the top
-//                         ~log2(n) - 1 varying bits (three 9-bit digits at 250M rows); k_local_bounds
-//                         cuts the result into ~2048-row tiles at run starts and k_sort_local ranks
-//                         every run of equal prefixes (a few rows) by full key in LDS and writes the
-//                         user columns.  A run longer than 256 rows (skewed keys) sends the
-//                         call to 8-bit digit passes over every varying byte (LSD, the same kernels),
-//                         which is also GM_PARAM_SORT_MODE 1.
-// The range scan over a sorted table (gm_key_range_scan) lives with the other row-filter scans in
-// gm_filter.hip.
-#include <string.h>
-
+// A GeoMesa Z3 table is the set of row keys [shard?][bin BE16][z BE64][id] kept in byte order by the store
+// (Z3IndexKeySpace.toIndexKey, idx/index/z3/Z3IndexKeySpace.scala:63-95); a query seeks each byte range
+// getRangeBytes produces (Z3IndexKeySpace.scala:196-238).  Here the table is columnar and resident in HBM,
+// and gm_sort_keys is a stable sort of (shard u8, bin u16, z u64) in that byte order: K = shard:bin:z, 88 bits.
+//   k_key_or_and_sample, k_sort_count -- which bits of K vary (OR / AND), and every pass's digit counts;
+//   k_sort_pass  -- a one-sweep digit pass (a digit of <= 9 bits) over 8192-row tiles, into 16-B records;
+//   k_local_bounds, k_sort_local -- after passes over the top ~log2(n) - 1 varying bits (three 9-bit digits
+//                   at 250M rows), every run of equal prefixes (a few rows) ranked by full key in LDS;
+//   gm_sort_keys -- the driver, in named steps (SortCall).  A run longer than 256 rows (skewed keys) sends
+//                   the call to 8-bit passes over every varying byte (LSD), as does GM_PARAM_SORT_MODE 1.
+// The table's other key passes are in gm_key_table.hip, its range scan in gm_filter.hip.  KeyCols comes from
+// gm_keycols.hpp; no device code crosses units.
 #include <algorithm>
 #include <vector>
 
-#include "gm_scan.hpp"
+#include "gm_keycols.hpp"
 #include "gm_sort_plan.hpp"
 
 namespace gm {
 
-constexpr int STPB = 256;               // key-byte threads per block
 constexpr int MAXTAG = 16;              // pass tags per call: prefix passes + a fallback's digit passes
 
-// 24 bits of K = bs:z (bs = bin | shard << 16) from bit `off` (0 <= off < 88) up; a digit is the low 8
+// 24 bits of K = bs:z (bs = bin | shard << 16) from bit `off` (0 <= off < 88) up
 __device__ __forceinline__ uint32_t key_bits(uint32_t bs, uint64_t z, int off) {
   uint64_t v;
   if (off >= 64) v = (uint64_t)bs >> (off - 64);
@@ -45,7 +32,6 @@ __device__ __forceinline__ uint32_t key_bits(uint32_t bs, uint64_t z, int off) {
   }
   return (uint32_t)v & 0xffffffu;
 }
-__device__ __forceinline__ uint32_t key_digit(uint32_t bs, uint64_t z, int off) { return key_bits(bs, z, off) & 255u; }
 
 // a row in flight between passes: {z lo, z hi, input row, bs} (bs = bin | shard << sq, squeeze_bs)
 __device__ __forceinline__ uint64_t rec_z(uint4 r) { return (uint64_t)r.x | ((uint64_t)r.y << 32); }
@@ -63,30 +49,34 @@ __device__ __forceinline__ uint32_t squeeze_bs(uint32_t b, int sq) { return (b &
 __device__ __forceinline__ uint16_t bs_bin(uint32_t w, int sq, uint32_t binhi) {
   return (uint16_t)((w & ((1u << sq) - 1u)) | binhi);
 }
-__device__ __forceinline__ uint64_t lanemask_lt() {
-  const int lane = threadIdx.x & 63;
-  return lane ? (~0ull >> (64 - lane)) : 0ull;
-}
-
-// The caller's columns.  bs = bin | shard << 16.
-struct KeyCols {
-  const uint8_t* sh;
-  const uint16_t* bin;
-  const uint64_t* z;
-};
 
 // which digit passes carry information: the OR and the AND of every key column (a digit on which
 // OR == AND is the same for every key, so its pass would be the identity and is skipped).
-// acc[0] = OR z, acc[1] = OR bs, acc[2] = AND z, acc[3] = AND bs.  Four pairs per lane in flight.
 __device__ __forceinline__ uint64_t wave_or(uint64_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
   return v;
 }
-__device__ __forceinline__ uint64_t wave_and(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v &= __shfl_xor(v, o, 64);
-  return v;
+__device__ __forceinline__ uint64_t wave_and(uint64_t v) { return ~wave_or(~v); }
+// the block's OR (zo, bo) and AND (za, ba) of z and bs into acc[0..3] = OR z, OR bs, AND z, AND bs: per wave, then through
+// LDS one device atomic per value per block (not per wave: same 4 addresses).  Every thread calls it: one block barrier.
+template <int NWAVE>
+__device__ __forceinline__ void block_or_and(uint64_t zo, uint64_t bo, uint64_t za, uint64_t ba,
+                                             unsigned long long* __restrict__ acc) {
+  __shared__ uint64_t s_oa[NWAVE][4];
+  zo = wave_or(zo); za = wave_and(za); bo = wave_or(bo); ba = wave_and(ba);
+  if ((threadIdx.x & 63) == 0) {
+    uint64_t* e = s_oa[threadIdx.x >> 6];
+    e[0] = zo; e[1] = bo; e[2] = za; e[3] = ba;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int j = threadIdx.x;
+    uint64_t v = s_oa[0][j];
+    for (int w = 1; w < NWAVE; ++w) v = j < 2 ? (v | s_oa[w][j]) : (v & s_oa[w][j]);
+    if (j < 2) atomicOr(&acc[j], (unsigned long long)v);
+    else atomicAnd(&acc[j], (unsigned long long)v);
+  }
 }
 // f(z, bs) over every row of the caller's columns, one wave per 512-row chunk.  With 16-B aligned
 // columns (`wide`) every load is one contiguous 1 KiB per wave instruction: z as 16-B pairs (rows
@@ -117,8 +107,7 @@ __device__ __forceinline__ void for_rows(const KeyCols& c, int64_t n, int wide, 
       }
       wave_lds_sync();   // the slice is free for the next chunk
     } else {
-      for (int64_t r = r0 + lane; r < min(n, r0 + RCH); r += 64)
-        f(c.z[r], (uint32_t)c.bin[r] | (SH ? (uint32_t)c.sh[r] << 16 : 0u));
+      for (int64_t r = r0 + lane; r < min(n, r0 + RCH); r += 64) f(c.z[r], c.bs<SH>(r));
     }
   }
 }
@@ -133,38 +122,26 @@ __global__ __launch_bounds__(256) void k_key_or_and_sample(KeyCols c, int64_t n,
   const int64_t step = n > SAMPLE ? n / SAMPLE : 1;
   uint64_t zo = 0, za = ~0ull, bo = 0, ba = ~0ull;
   auto take = [&](int64_t r) {
-    const uint64_t z = c.z[r];
-    const uint32_t b = (uint32_t)c.bin[r] | (SH ? (uint32_t)c.sh[r] << 16 : 0u);
+    const uint64_t z = c.z[r], b = c.bs<SH>(r);
     zo |= z; za &= z; bo |= b; ba &= b;
   };
   if (i < SAMPLE && i * step < n) take(i * step);
   if (i == 0) take(n - 1);
-  __shared__ uint64_t s_oa[4][4];
-  zo = wave_or(zo); za = wave_and(za); bo = wave_or(bo); ba = wave_and(ba);
-  if ((threadIdx.x & 63) == 0) {
-    uint64_t* e = s_oa[threadIdx.x >> 6];
-    e[0] = zo; e[1] = bo; e[2] = za; e[3] = ba;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const int j = threadIdx.x;
-    uint64_t v = s_oa[0][j];
-    for (int w = 1; w < 4; ++w) v = j < 2 ? (v | s_oa[w][j]) : (v & s_oa[w][j]);
-    if (j < 2) atomicOr(&acc[j], (unsigned long long)v);
-    else atomicAnd(&acc[j], (unsigned long long)v);
-  }
+  block_or_and<4>(zo, bo, za, ba, acc);
 }
 
 // Every pass's digit counts in one read: counts[base_k + d] = rows whose digit k (bits [off_k, off_k +
 // w_k) of K) is d, base_k = k * 512.  Four LDS copies of the counters (by wave) cut the atomic
-// collisions.  ORAND: the same read also takes the exact OR / AND of the key columns into
-// acc[0..3] = OR z, OR bs, AND z, AND bs (bs = bin | shard << 16).
+// collisions.  ORAND: the same read also takes the exact OR / AND of the caller's columns (block_or_and).
 constexpr int NB_MAX = 1 << WMAX;
 __device__ __forceinline__ uint32_t key_digit_w(uint32_t bs, uint64_t z, int off, int w) {
   return key_bits(bs, z, off) & ((1u << w) - 1u);
 }
 constexpr int CNT_LDS = 2816;           // 11 byte digits x 256, or 4 prefix digits x 512 (<= 2048)
 constexpr int CT = 1024;   // count threads per block
+#ifndef GM_SORT_CGRID   // count blocks: 1024 vs 512 -0.04 ms per sort, 256 +0.07 (profiles/r5/sort_count_grid_ab.txt)
+#define GM_SORT_CGRID 1024
+#endif
 template <bool SH, bool ORAND>
 __global__ __launch_bounds__(CT) void k_sort_count(KeyCols c, int64_t n, DigitOffs o, uint32_t* __restrict__ counts, int wide,
                                                    unsigned long long* __restrict__ acc, int sq) {
@@ -179,22 +156,8 @@ __global__ __launch_bounds__(CT) void k_sort_count(KeyCols c, int64_t n, DigitOf
     for (int k = 0, bk = 0; k < o.np; bk += 1 << o.w[k], ++k)
       atomicAdd(&h[copy][bk + key_digit_w(bk_s, z, o.off[k], o.w[k])], 1u);
   });
-  __shared__ uint64_t s_oa[ORAND ? CT / 64 : 1][4];
-  if (ORAND) {   // per wave, then one device atomic per value per block (not per wave: same 4 addresses)
-    zo = wave_or(zo); za = wave_and(za); bo = wave_or(bo); ba = wave_and(ba);
-    if ((threadIdx.x & 63) == 0) {
-      uint64_t* e = s_oa[threadIdx.x >> 6];
-      e[0] = zo; e[1] = bo; e[2] = za; e[3] = ba;
-    }
-  }
-  __syncthreads();
-  if (ORAND && threadIdx.x < 4) {
-    const int j = threadIdx.x;
-    uint64_t v = s_oa[0][j];
-    for (int w = 1; w < CT / 64; ++w) v = j < 2 ? (v | s_oa[w][j]) : (v & s_oa[w][j]);
-    if (j < 2) atomicOr(&acc[j], (unsigned long long)v);
-    else atomicAnd(&acc[j], (unsigned long long)v);
-  }
+  if (ORAND) block_or_and<CT / 64>(zo, bo, za, ba, acc);   // its barrier also closes the counting
+  else __syncthreads();
   for (int k = 0, bk = 0; k < o.np; bk += 1 << o.w[k], ++k)
     for (int d = threadIdx.x; d < (1 << o.w[k]); d += CT) {
       const int i = bk + d;
@@ -210,12 +173,11 @@ __global__ __launch_bounds__(CT) void k_sort_count(KeyCols c, int64_t n, DigitOf
 // per-wave LDS counter per digit turns half ranks into wave ranks, a scan over the waves into tile
 // ranks, so a row's place in the tile is (digit, wave, slot, half, lane) = stable.  The tile's digit
 // offsets in the output are the digit's global start plus its rows in every lower tile: thread d
-// publishes digit d's tile count as
-// soon as the tile is ranked ({count, AGG} granule, one 8-B write-through store), then walks back over
-// the lower tiles' granules, adding counts until it meets an inclusive prefix (PRE), and publishes its
-// own (decoupled look-back).  The tile is reordered in LDS meanwhile and leaves as digit runs of 16-B
-// records.  Granule tags carry the pass (tag) so no pass reads another's; the status array is cleared
-// once per call.  1024-thread blocks over 8192-row tiles (LDS ~148 KB: one block, 16 waves, per CU):
+// publishes digit d's tile count as soon as the tile is ranked ({count, AGG} granule, one 8-B write-through
+// store), then walks back over the lower tiles' granules, adding counts until it meets an inclusive prefix
+// (PRE), and publishes its own (decoupled look-back).  The tile is reordered in LDS meanwhile and leaves as
+// digit runs of 16-B records.  Granule tags carry the pass (tag) so no pass reads another's; the status array
+// is cleared once per call.  1024-thread blocks over 8192-row tiles (LDS ~148 KB: one block, 16 waves, per CU):
 // 10.84-10.86 -> 10.48-10.51 ms per 250M-row sort against 512 threads / 4096 rows at two blocks per CU
 // once the tile's loads were all in flight together (profiles/r5/sort_tile_shape_ab.txt; 768 threads
 // 11.97-11.99, 1024 x 2048 rows 13.75-13.77, 1024 x 6144 11.63-11.67, 512 x 8192 11.30-11.35).
@@ -236,10 +198,7 @@ constexpr int LB = GM_SORT_LB;   // look-back granules per round trip
 struct PassArgs {
   KeyCols in;             // the caller's columns (first pass) ...
   const uint4* rec_in;    // ... or the previous pass's records
-  uint8_t* sh_out;        // the caller's outputs (last pass) ...
-  uint16_t* bin_out;
-  uint64_t* z_out;
-  int64_t* perm_out;
+  uint8_t* sh_out; uint16_t* bin_out; uint64_t* z_out; int64_t* perm_out;   // the caller's outputs (last pass) ...
   uint4* rec_out;         // ... or records
   int64_t n;
   int off, w;             // digit: bits [off, off + w) of K
@@ -268,47 +227,29 @@ __global__ __launch_bounds__(PT) void k_sort_pass(PassArgs a) {
   for (int i = t; i < PW * NB_MAX / 2; i += PT) ((uint32_t*)&s_wcnt[0][0])[i] = 0u;
   __syncthreads();
   const int64_t tile = s_tile, t0 = tile * PTILE, n = a.n;
-  // this lane's rows: slot k of wave w holds rows r = t0 + 512 w + 128 k + lane (A) and r + 64 (B), so
-  // in input order a slot is its 64 A rows, then its 64 B rows, and each half ranks like one row per
-  // lane, with one mask per row.  (Pairs (2 lane, 2 lane + 1) would interleave the halves and need four
-  // cross masks per pair: ~80 instead of ~45 VALU per row with ballots, profiles/r6.)
+  // this lane's rows: slot k of wave w holds rows r = t0 + 512 w + 128 k + lane (A) and r + 64 (B), so in input order a
+  // slot is its 64 A rows, then its 64 B rows, and each half ranks like one row per lane, with one mask per row.  (Pairs
+  // (2 lane, 2 lane + 1) would interleave the halves: four cross masks per pair, ~80 not ~45 VALU per row, profiles/r6.)
   uint4 rv[PSLOT][2];
   const bool full = t0 + PTILE <= n;   // every tile but the last (uniform)
-  const bool vec = a.vec && full;
-  if (IN_REC && full) {
-    // a full tile's loads are unconditional, so the compiler counts them: all 2 * PSLOT are in flight
-    // before the first wait
-#pragma unroll
-    for (int k = 0; k < PSLOT; ++k) {
-      const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + lane;
-      rv[k][0] = a.rec_in[i];
-      rv[k][1] = a.rec_in[i + 64];
-    }
-  } else if (!IN_REC && vec) {   // the same for the first pass's column loads
+  auto row = [&](int k, int e) -> int64_t { return t0 + wave * (2 * 64 * PSLOT) + k * 128 + 64 * e + lane; };
+  auto rec = [&](int64_t i) -> uint4 {   // row i: the previous pass's record, or one from the caller's columns
+    if (IN_REC) return a.rec_in[i];
+    uint32_t b = a.in.bs<SH>(i);
+    if (SH) b = squeeze_bs(b, a.sq);
+    return make_rec(a.in.z[i], (uint32_t)i, b);
+  };
+  auto load = [&](auto get) {
 #pragma unroll
     for (int k = 0; k < PSLOT; ++k)
 #pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 64 * e + lane;
-        uint32_t b = (uint32_t)a.in.bin[i];
-        if (SH) b = squeeze_bs(b | (uint32_t)a.in.sh[i] << 16, a.sq);
-        rv[k][e] = make_rec(a.in.z[i], (uint32_t)i, b);
-      }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PSLOT; ++k)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 64 * e + lane;
-        if (IN_REC) {
-          rv[k][e] = i < n ? a.rec_in[i] : make_uint4(0u, 0u, 0u, 0u);
-        } else {
-          uint32_t b = i < n ? (uint32_t)a.in.bin[i] | (SH ? (uint32_t)a.in.sh[i] << 16 : 0u) : 0u;
-          if (SH) b = squeeze_bs(b, a.sq);
-          rv[k][e] = make_rec(i < n ? a.in.z[i] : 0ull, (uint32_t)i, b);
-        }
-      }
-  }
+      for (int e = 0; e < 2; ++e) rv[k][e] = get(row(k, e));
+  };
+  // Three load shapes.  A full tile of records and a full tile of aligned columns (a.vec) load unconditionally,
+  // so the compiler counts the loads: all 2 * PSLOT are in flight before the first wait.  Any other tile is
+  // guarded row by row (a lane without a row holds zeros and ranks nothing).
+  if (full && (IN_REC || a.vec)) load(rec);
+  else load([&](int64_t i) { return i < n ? rec(i) : make_uint4(0u, 0u, 0u, 0u); });
   const uint64_t lt = lanemask_lt();
   uint32_t rd[PSLOT][2];   // wave rank | digit << 16; rank 0xffff = no row
   // lanes sharing a digit found through LDS instead of 9 ballot rounds: each row ORs its lane bit into
@@ -322,8 +263,7 @@ __global__ __launch_bounds__(PT) void k_sort_pass(PassArgs a) {
   for (int k = 0; k < PSLOT; ++k)
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const int64_t i = t0 + wave * (2 * 64 * PSLOT) + k * 128 + 64 * e + lane;
-      const bool ok = i < n;
+      const bool ok = row(k, e) < n;
       const uint32_t d = key_digit_w(rv[k][e].w, rec_z(rv[k][e]), a.off, w);
       if (ok) atomicOr((unsigned long long*)&mslot[d], 1ull << lane);
       wave_lds_sync();
@@ -595,506 +535,182 @@ __global__ __launch_bounds__(STPB) void k_widen_perm(int64_t n, int64_t* __restr
   for (int64_t i = (int64_t)blockIdx.x * STPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * STPB) p64[i] = i;
 }
 
-// ------------------------------------------------------------------ row-key bytes
-// 256 rows per block: each thread writes its row's bytes into LDS, then the block's contiguous
-// 256 * key_len bytes (a multiple of 16) leave with 16-B stores.
-__global__ __launch_bounds__(STPB) void k_key_bytes(const uint8_t* __restrict__ sh, const int16_t* __restrict__ bin,
-                                                    const int64_t* __restrict__ z, int64_t n, int klen,
-                                                    uint8_t* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint8_t s[STPB * 11];
-  const int64_t r0 = (int64_t)blockIdx.x * STPB;
-  const int64_t i = r0 + threadIdx.x;
-  if (i < n) {
-    uint8_t* o = s + threadIdx.x * klen;
-    int k = 0;
-    if (sh) o[k++] = sh[i];
-    if (bin) {   // no bin: the Z2 / XZ2 layout [shard][z BE64]
-      const uint16_t b = (uint16_t)bin[i];
-      o[k++] = (uint8_t)(b >> 8);
-      o[k++] = (uint8_t)b;
-    }
-    const uint64_t zz = (uint64_t)z[i];
-#pragma unroll
-    for (int j = 7; j >= 0; --j) o[k++] = (uint8_t)(zz >> (8 * j));
-  }
-  __syncthreads();
-  const int64_t rows = min((int64_t)STPB, n - r0);
-  const int64_t bytes = rows * klen;
-  uint8_t* dst = out + r0 * klen;
-  if (rows == STPB && (((uintptr_t)dst) & 15u) == 0) {
-    const uint4* s4 = (const uint4*)s;
-    uint4* d4 = (uint4*)dst;
-    for (int j = threadIdx.x; j < bytes / 16; j += STPB) d4[j] = s4[j];
-  } else {
-    for (int64_t j = threadIdx.x; j < bytes; j += STPB) dst[j] = s[j];
-  }
-}
-
-// ------------------------------------------------------------------ key-range partition (multi-GPU ingest)
-// A table split into `nd` contiguous key ranges (tablets / regions; one per GPU) by nd - 1 ascending
-// splitter keys: row r goes to destination d = the number of splitters <= its key (a key equal to a
-// splitter opens the upper range).  Keys compare as the row bytes do: (shard << 16 | bin as u16, z as
-// u64), unsigned.  One read counts every tile's rows per destination (k_part_count), a device scan of
-// those counts in destination-major order gives each (destination, tile) its output start, and a
-// second read (k_part_scatter) ranks the tile's rows per destination in LDS (wave ballots, stable:
-// within a destination rows keep their input order) and writes them as contiguous destination runs,
-// so that destination d's rows are one slice of every output column -- what one all-to-all sends.
-constexpr int XT = 256;                  // partition threads per block
-constexpr int XTILE = 2048;              // rows per tile: wave w owns rows [512 w, 512 w + 512)
-constexpr int XSLOT = XTILE / XT;        // 8 rows per lane, one per 64-row slot
-constexpr int XMAX = 256;                // destinations at most (ranks of the partitioned table)
-
-struct SplitLds {
-  uint32_t hi[XMAX];
-  uint64_t lo[XMAX];
-};
-// destination of key (hi, lo): first splitter greater than the key (binary search, ns < XMAX)
-__device__ __forceinline__ int part_dest(const SplitLds& s, int ns, uint32_t hi, uint64_t lo) {
-  int a = 0, b = ns;
-  while (a < b) {
-    const int m = (a + b) >> 1;
-    const bool le = s.hi[m] < hi || (s.hi[m] == hi && s.lo[m] <= lo);
-    if (le) a = m + 1;
-    else b = m;
-  }
-  return a;
-}
-__device__ __forceinline__ void load_splitters(SplitLds& s, const uint64_t* __restrict__ split, int ns) {
-  for (int k = threadIdx.x; k < ns; k += blockDim.x) {
-    s.hi[k] = (uint32_t)split[2 * k];
-    s.lo[k] = split[2 * k + 1];
-  }
-}
-// lanes of this wave whose destination equals mine (among the lanes with `ok`), from nbits ballots
-__device__ __forceinline__ uint64_t match_dest(uint32_t d, bool ok, int nbits) {
-  uint64_t m = __ballot(ok);
-  for (int bit = 0; bit < nbits; ++bit) {   // uniform
-    const uint64_t b = __ballot((d >> bit) & 1u);
-    m &= ((d >> bit) & 1u) ? b : ~b;
-  }
-  return m;
-}
-template <bool SH>
-__device__ __forceinline__ void part_load_tile(const KeyCols& c, int64_t t0, int64_t n, uint64_t (&z)[XSLOT],
-                                               uint32_t (&bs)[XSLOT]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t r0 = t0 + wave * (64 * XSLOT) + lane;
-  if (t0 + XTILE <= n) {   // uniform: a full tile's loads are unconditional, all in flight together
-#pragma unroll
-    for (int s = 0; s < XSLOT; ++s) {
-      z[s] = c.z[r0 + 64 * s];
-      bs[s] = (uint32_t)c.bin[r0 + 64 * s] | (SH ? (uint32_t)c.sh[r0 + 64 * s] << 16 : 0u);
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < XSLOT; ++s) {
-      const int64_t r = r0 + 64 * s;
-      z[s] = r < n ? c.z[r] : 0ull;
-      bs[s] = r < n ? ((uint32_t)c.bin[r] | (SH ? (uint32_t)c.sh[r] << 16 : 0u)) : 0u;
-    }
-  }
-}
-
-// cnt[d * ntiles + tile] = rows of the tile bound for d (destination-major: the exclusive scan of cnt
-// is each (destination, tile)'s first output row; the destinations' totals come from that scan, not from
-// per-block device atomics -- eight counters taking one atomic per block each serialised the count pass:
-// 1.59 ms per 250M rows)
-template <bool SH>
-__global__ __launch_bounds__(XT) void k_part_count(KeyCols c, int64_t n, const uint64_t* __restrict__ split, int ns,
-                                                   int nbits, uint32_t* __restrict__ cnt, int64_t ntiles) {
-  __shared__ SplitLds s_sp;
-  __shared__ uint32_t s_c[XMAX];
-  const int nd = ns + 1, lane = threadIdx.x & 63;
-  load_splitters(s_sp, split, ns);
-  for (int d = threadIdx.x; d < nd; d += XT) s_c[d] = 0u;
-  __syncthreads();
-  const int64_t tile = blockIdx.x, t0 = tile * XTILE;
-  uint64_t z[XSLOT];
-  uint32_t bs[XSLOT];
-  part_load_tile<SH>(c, t0, n, z, bs);
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < XSLOT; ++s) {
-    const bool ok = t0 + wave * (64 * XSLOT) + 64 * s + lane < n;
-    const uint32_t d = ok ? (uint32_t)part_dest(s_sp, ns, bs[s], z[s]) : 0u;
-    const uint64_t m = match_dest(d, ok, nbits);
-    if (ok && (m & lanemask_lt()) == 0) atomicAdd(&s_c[d], (uint32_t)__popcll(m));   // one add per destination
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < nd; d += XT) cnt[(int64_t)d * ntiles + tile] = s_c[d];
-}
-
-// each destination's row count from the destination-major scan: start of d = offs[d * ntiles]
-__global__ __launch_bounds__(XMAX) void k_part_totals(const int64_t* __restrict__ offs, int64_t ntiles, int nd,
-                                                      const int64_t* __restrict__ total, int64_t* __restrict__ out) {
-  const int d = threadIdx.x;
-  if (d < nd) out[d] = (d + 1 < nd ? offs[(int64_t)(d + 1) * ntiles] : *total) - offs[(int64_t)d * ntiles];
-}
-
-// The tile ranked per destination in LDS and written as destination runs.  offs = the exclusive scan
-// of k_part_count's cnt.  Per row: z_out, bin_out, shard_out (SH), and the row's source as ids_out =
-// ids[row] (IDS) or id_base + row, and / or rows_out = row (u32); either output may be null.
-template <bool SH, bool IDS>
-__global__ __launch_bounds__(XT) void k_part_scatter(KeyCols c, int64_t n, const uint64_t* __restrict__ split, int ns,
-                                                     int nbits, const int64_t* __restrict__ offs, int64_t ntiles,
-                                                     const int64_t* __restrict__ ids, int64_t id_base,
-                                                     int64_t* __restrict__ ids_out, uint32_t* __restrict__ rows_out,
-                                                     uint8_t* __restrict__ sh_out, uint16_t* __restrict__ bin_out,
-                                                     uint64_t* __restrict__ z_out) {
-  __shared__ SplitLds s_sp;
-  __shared__ uint4 s_rec[XTILE];                 // {z lo, z hi, bs, tile row | destination << 16}
-  __shared__ uint16_t s_wcnt[XT / 64][XMAX];     // per wave: rows of each destination (then: wave offsets)
-  __shared__ uint32_t s_dstart[XMAX];            // the destination's first slot in the tile
-  __shared__ int64_t s_g[XMAX];                  // output row of tile slot q = s_g[d] + q
-  __shared__ uint32_t s_wsum[XT / 64];
-  const int nd = ns + 1, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  load_splitters(s_sp, split, ns);
-  for (int i = t; i < (XT / 64) * XMAX; i += XT) (&s_wcnt[0][0])[i] = 0;
-  __syncthreads();
-  const int64_t tile = blockIdx.x, t0 = tile * XTILE;
-  uint64_t z[XSLOT];
-  uint32_t bs[XSLOT];
-  part_load_tile<SH>(c, t0, n, z, bs);
-  uint32_t rd[XSLOT];   // wave rank | destination << 16; rank 0xffff = no row
-  const uint64_t lt = lanemask_lt();
-#pragma unroll
-  for (int s = 0; s < XSLOT; ++s) {
-    const bool ok = t0 + wave * (64 * XSLOT) + 64 * s + lane < n;
-    const uint32_t d = ok ? (uint32_t)part_dest(s_sp, ns, bs[s], z[s]) : 0u;
-    const uint64_t m = match_dest(d, ok, nbits);
-    const int r = __popcll(m & lt);
-    const uint32_t c0 = s_wcnt[wave][d];
-    rd[s] = (ok ? c0 + r : 0xffffu) | (d << 16);
-    __builtin_amdgcn_wave_barrier();
-    if (ok && r == 0) s_wcnt[wave][d] = (uint16_t)(c0 + __popcll(m));
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  // thread d: its wave offsets and tile total, then a block scan of the totals over destinations
-  uint32_t tot = 0;
-  if (t < nd) {
-#pragma unroll
-    for (int v = 0; v < XT / 64; ++v) {
-      const uint32_t cv = s_wcnt[v][t];
-      s_wcnt[v][t] = (uint16_t)tot;
-      tot += cv;
-    }
-  }
-  uint32_t x = tot;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wsum[wave] = x;
-  __syncthreads();
-  if (t < nd) {
-    uint32_t p = 0;
-    for (int v = 0; v < wave; ++v) p += s_wsum[v];
-    const uint32_t ds = p + x - tot;
-    s_dstart[t] = ds;
-    s_g[t] = offs[(int64_t)t * ntiles + tile] - (int64_t)ds;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < XSLOT; ++s) {
-    const uint32_t r = rd[s] & 0xffffu, d = rd[s] >> 16;
-    if (r == 0xffffu) continue;
-    const uint32_t row = (uint32_t)(wave * (64 * XSLOT) + 64 * s + lane);
-    s_rec[s_dstart[d] + s_wcnt[wave][d] + r] = make_uint4((uint32_t)z[s], (uint32_t)(z[s] >> 32), bs[s], row | (d << 16));
-  }
-  __syncthreads();
-  const int cntt = (int)min((int64_t)XTILE, n - t0);
-  for (int q = t; q < cntt; q += XT) {
-    const uint4 v = s_rec[q];
-    const int64_t g = s_g[v.w >> 16] + q;
-    const int64_t row = t0 + (v.w & 0xffffu);
-    z_out[g] = (uint64_t)v.x | ((uint64_t)v.y << 32);
-    bin_out[g] = (uint16_t)v.z;
-    if (SH) sh_out[g] = (uint8_t)(v.z >> 16);
-    if (ids_out) ids_out[g] = IDS ? ids[row] : id_base + row;
-    if (rows_out) rows_out[g] = (uint32_t)row;
-  }
-}
-
-// n_samples keys at rows floor((2i + 1) n / (2 n_samples)): out[2i] = shard << 16 | bin (u16), out[2i + 1] = z
-template <bool SH>
-__global__ __launch_bounds__(256) void k_key_sample(KeyCols c, int64_t n, int ns, uint64_t* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= ns) return;
-  const int64_t r = (int64_t)((uint64_t)(2 * i + 1) * (uint64_t)n / (2 * (uint64_t)ns));   // < 2^49: ns <= 2^16, n < 2^32
-  out[2 * i] = (uint64_t)c.bin[r] | (SH ? (uint64_t)c.sh[r] << 16 : 0ull);
-  out[2 * i + 1] = c.z[r];
-}
-
 }  // namespace gm
 
 using namespace gm;
 
-extern "C" {
+namespace {
 
-int gm_z3_key_bytes(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n, uint8_t* out) {
-  if (!ctx || n < 0) return GM_E_INVALID;
-  if (n == 0) return GM_OK;
-  if (!bin || !z || !out) return GM_E_INVALID;
-  const int klen = shard ? 11 : 10;
-  hipLaunchKernelGGL(k_key_bytes, dim3((unsigned)((n + STPB - 1) / STPB)), dim3(STPB), 0, ctx->stream, shard, bin, z,
-                     n, klen, out);
-  GM_CHECK_LAUNCH();
+// The sort's slots of ctx->d_scratch (u64 each).  An OR / AND set is {OR z, OR bs, AND z, AND bs} of the
+// caller's keys: 0..3 of every key (k_sort_count), 8..11 of the sample (k_key_or_and_sample); 4 is the flag
+// of a run of equal prefixes too long to rank locally (k_local_bounds, k_sort_local)
+constexpr int ACC_EXACT = 0, ACC_FLAG = 4, ACC_SAMPLE = 8;
+
+// Z2 / XZ2 tables have no time bin: the sort runs over a zero bin column (constant, so no digit pass looks
+// at it) and its bin output goes to scratch
+int zero_bin(gm_ctx* ctx, int64_t n, const int16_t** bin, int16_t** bin_out) {
+  Carve c{16};
+  const size_t o_in = c.take((size_t)n * 2), o_out = c.take((size_t)n * 2);
+  char* zb = nullptr;
+  const int rc = ctx_workspace(ctx, WS_SCAN, c.total, (void**)&zb);
+  if (rc) return rc;
+  *bin = (const int16_t*)(zb + o_in); *bin_out = (int16_t*)(zb + o_out);
+  GM_HIP(hipMemsetAsync(zb + o_in, 0, (size_t)n * 2, ctx->stream));
   return GM_OK;
 }
 
-int gm_z2_key_bytes(gm_ctx* ctx, const uint8_t* shard, const int64_t* z, int64_t n, uint8_t* out) {
-  if (!ctx || n < 0) return GM_E_INVALID;
-  if (n == 0) return GM_OK;
-  if (!z || !out) return GM_E_INVALID;
-  hipLaunchKernelGGL(k_key_bytes, dim3((unsigned)((n + STPB - 1) / STPB)), dim3(STPB), 0, ctx->stream, shard, nullptr, z,
-                     n, shard ? 9 : 8, out);
-  GM_CHECK_LAUNCH();
-  return GM_OK;
-}
-
-int gm_sort_keys(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
-                 uint8_t* shard_out, int16_t* bin_out, int64_t* z_out, int64_t* perm_out) {
-  if (!ctx || n < 0 || n > (int64_t)UINT32_MAX) return GM_E_INVALID;
-  if (n == 0) return GM_OK;
-  if (!z || !z_out || !perm_out || ((shard == nullptr) != (shard_out == nullptr)) ||
-      ((bin == nullptr) != (bin_out == nullptr)))
-    return GM_E_INVALID;
-  hipStream_t s = ctx->stream;
-  if (!bin) {
-    // no time bin (Z2 / XZ2 tables): the sort runs over a zero bin column (constant, so no digit pass
-    // looks at it) and its bin output goes to scratch
+// The context's sort workspace: records x 2 | look-back granules (ntiles x NB_MAX) | digit counts (by tag) |
+// tile counters (by tag) | local bounds, 16-B aligned
+constexpr size_t COUNTS_BYTES = (size_t)MAXTAG * NB_MAX * 4;
+struct SortWs {
+  uint4* rec[2];
+  unsigned long long* status; uint32_t* counts; unsigned int* ctr; int64_t* lbounds;
+  int take(gm_ctx* ctx, int64_t n) {
     Carve c{16};
-    const size_t o_in = c.take((size_t)n * 2), o_out = c.take((size_t)n * 2);
-    char* zb = nullptr;
-    int rc = ctx_workspace(ctx, WS_SCAN, c.total, (void**)&zb);
-    if (rc) return rc;
-    bin = (const int16_t*)(zb + o_in);
-    bin_out = (int16_t*)(zb + o_out);
-    GM_HIP(hipMemsetAsync(zb + o_in, 0, (size_t)n * 2, s));
-  }
-  const uint8_t* sh = shard;
-  const KeyCols in{sh, (const uint16_t*)bin, (const uint64_t*)z};
-  // aligned caller columns: the first pass then loads a full tile's rows unconditionally
-  const int user_vec = ((uintptr_t)z % 16) == 0 && ((uintptr_t)bin % 4) == 0 && (!sh || ((uintptr_t)sh % 2) == 0);
-  // 16-B loads of every column in the OR/AND and count reads
-  const int user_wide = ((uintptr_t)z % 16) == 0 && ((uintptr_t)bin % 16) == 0 && (!sh || ((uintptr_t)sh % 16) == 0);
-  const int64_t nchunk = (n + RCH - 1) / RCH;
-#ifndef GM_SORT_CGRID   // count blocks: 1024 vs 512 -0.04 ms per sort, 256 +0.07 (profiles/r5/sort_count_grid_ab.txt)
-#define GM_SORT_CGRID 1024
-#endif
-  const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>(GM_SORT_CGRID, (nchunk + CT / 64 - 1) / (CT / 64)));
-  const int64_t ntiles = (n + PTILE - 1) / PTILE;
-  uint4 *rec[2] = {nullptr, nullptr};
-  unsigned long long* status = nullptr;
-  uint32_t* counts = nullptr;
-  unsigned int* ctr = nullptr;
-  int64_t* lbounds = nullptr;
-  size_t counts_bytes = 0;
-  {  // context-owned workspace: records x 2 | granules | counts | tile counters | local bounds, 16-B aligned
-    Carve c{16};
-    const size_t o_r0 = c.take((size_t)n * 16), o_r1 = c.take((size_t)n * 16), o_st = c.take((size_t)ntiles * NB_MAX * 8),
-                 o_c = c.take((size_t)MAXTAG * NB_MAX * 4), o_t = c.take((size_t)MAXTAG * 4),
-                 o_b = c.take((size_t)((n + LSTEP - 1) / LSTEP + 1) * 8);
+    const size_t o_r0 = c.take((size_t)n * 16), o_r1 = c.take((size_t)n * 16),
+                 o_st = c.take((size_t)((n + PTILE - 1) / PTILE) * NB_MAX * 8), o_c = c.take(COUNTS_BYTES),
+                 o_t = c.take((size_t)MAXTAG * 4), o_b = c.take((size_t)((n + LSTEP - 1) / LSTEP + 1) * 8);
     char* base = nullptr;
-    int wrc = ctx_workspace(ctx, WS_SORT, c.total, (void**)&base);
-    if (wrc) return wrc;
-    rec[0] = (uint4*)(base + o_r0);
-    rec[1] = (uint4*)(base + o_r1);
-    status = (unsigned long long*)(base + o_st);
-    counts = (uint32_t*)(base + o_c);
-    ctr = (unsigned int*)(base + o_t);
-    lbounds = (int64_t*)(base + o_b);
-    counts_bytes = o_t - o_c;
-    GM_HIP(hipMemsetAsync(status, 0, o_b - o_st, s));   // granules (tag 0 = none), counts, counters: adjacent
+    const int rc = ctx_workspace(ctx, WS_SORT, c.total, (void**)&base);
+    if (rc) return rc;
+    rec[0] = (uint4*)(base + o_r0); rec[1] = (uint4*)(base + o_r1);
+    status = (unsigned long long*)(base + o_st); counts = (uint32_t*)(base + o_c);
+    ctr = (unsigned int*)(base + o_t); lbounds = (int64_t*)(base + o_b);
+    GM_HIP(hipMemsetAsync(status, 0, o_b - o_st, ctx->stream));   // granules (tag 0 = none), counts, counters: adjacent
+    return GM_OK;
   }
-  // which key bits vary: acc[0..3] = OR z, OR bs, AND z, AND bs of every key (k_sort_count), acc[8..11]
-  // the same over a sample (k_key_or_and_sample), acc[4] k_sort_local's flag
-  unsigned long long* acc = (unsigned long long*)ctx->d_scratch;
-  GM_HIP(hipMemsetAsync(acc, 0, 16, s));
-  GM_HIP(hipMemsetAsync(acc + 2, 0xff, 16, s));
-  GM_HIP(hipMemsetAsync(acc + 4, 0, 8, s));
-  GM_HIP(hipMemsetAsync(acc + 8, 0, 16, s));
-  GM_HIP(hipMemsetAsync(acc + 10, 0xff, 16, s));
-  if (sh) hipLaunchKernelGGL(k_key_or_and_sample<true>, dim3(SAMPLE / 256), dim3(256), 0, s, in, n, acc + 8);
-  else hipLaunchKernelGGL(k_key_or_and_sample<false>, dim3(SAMPLE / 256), dim3(256), 0, s, in, n, acc + 8);
-  GM_CHECK_LAUNCH();
-  unsigned long long hs[4];
-  GM_HIP(hipMemcpyAsync(hs, acc + 8, sizeof(hs), hipMemcpyDeviceToHost, s));
-  GM_HIP(hipStreamSynchronize(s));
-  const SortPlan guess = plan_sort(hs, sh != nullptr, n, ctx->sort_mode);
-  // the guessed plan's first digit set counted in the read that takes the exact OR / AND
-  {
-    const DigitOffs o = guess.first_digits();
-    if (sh) hipLaunchKernelGGL((k_sort_count<true, true>), dim3(cgrid), dim3(CT), 0, s, in, n, o, counts, user_wide, acc, guess.sq);
-    else hipLaunchKernelGGL((k_sort_count<false, true>), dim3(cgrid), dim3(CT), 0, s, in, n, o, counts, user_wide, acc, 16);
+};
+
+// One validated gm_sort_keys call and the driver's steps
+struct SortCall {
+  gm_ctx* ctx; hipStream_t s;
+  unsigned long long* acc;   // ctx->d_scratch, by the ACC_ slots
+  KeyCols in; int64_t n;
+  uint8_t* sh_out; uint16_t* bin_out; uint64_t* z_out; int64_t* perm_out;
+  SortWs ws; SortPlan plan;
+  // digit counts of `o` into cnt, one read of every key; `orand`: the same read takes the exact OR / AND
+  int count(const DigitOffs& o, uint32_t* cnt, bool orand, int sq) {
+    const int wide = aligned16(in.z) && aligned16(in.bin) && aligned16(in.sh);   // 16-B loads of every column
+    const int64_t nchunk = (n + RCH - 1) / RCH;
+    const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>(GM_SORT_CGRID, (nchunk + CT / 64 - 1) / (CT / 64)));
+    with_flags([&](auto SH, auto ORAND) {
+      hipLaunchKernelGGL((k_sort_count<SH(), ORAND()>), dim3(cgrid), dim3(CT), 0, s, in, n, o, cnt, wide,
+                         ORAND() ? acc + ACC_EXACT : nullptr, sq);
+    }, in.sh != nullptr, orand);
     GM_CHECK_LAUNCH();
+    return GM_OK;
   }
-  unsigned long long hacc[4];
-  GM_HIP(hipMemcpyAsync(hacc, acc, sizeof(hacc), hipMemcpyDeviceToHost, s));
-  GM_HIP(hipStreamSynchronize(s));
-  const SortPlan plan = plan_sort(hacc, sh != nullptr, n, ctx->sort_mode);
-  const std::vector<int>& lsd = plan.lsd;
-  if (lsd.empty()) {  // every key equal: table order = input order
-    if (sh) GM_HIP(hipMemcpyAsync(shard_out, sh, (size_t)n, hipMemcpyDeviceToDevice, s));
-    GM_HIP(hipMemcpyAsync(bin_out, bin, (size_t)n * 2, hipMemcpyDeviceToDevice, s));
-    GM_HIP(hipMemcpyAsync(z_out, z, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+  // the plan of the OR / AND set at `slot`, read back (synchronises the stream)
+  int read_plan(int slot, SortPlan* p) {
+    unsigned long long h[4];
+    GM_HIP(hipMemcpyAsync(h, acc + slot, sizeof(h), hipMemcpyDeviceToHost, s));
+    GM_HIP(hipStreamSynchronize(s));
+    *p = plan_sort(h, in.sh != nullptr, n, ctx->sort_mode);
+    return GM_OK;
+  }
+  // Planning: the sample's OR / AND -> plan_sort -> that guess's first digit set counted in the read that
+  // takes the exact OR / AND -> plan_sort.  *counted: the exact bits give the same first digits, so their
+  // counts stand; else they are cleared and the passes count again.
+  int make_plan(bool* counted) {
+    GM_HIP(hipMemsetAsync(acc + ACC_EXACT, 0, 16, s));            // OR z, OR bs
+    GM_HIP(hipMemsetAsync(acc + ACC_EXACT + 2, 0xff, 16, s));     // AND z, AND bs
+    GM_HIP(hipMemsetAsync(acc + ACC_FLAG, 0, 8, s));
+    GM_HIP(hipMemsetAsync(acc + ACC_SAMPLE, 0, 16, s));
+    GM_HIP(hipMemsetAsync(acc + ACC_SAMPLE + 2, 0xff, 16, s));
+    with_flags([&](auto SH) {
+      hipLaunchKernelGGL(k_key_or_and_sample<SH()>, dim3(SAMPLE / 256), dim3(256), 0, s, in, n, acc + ACC_SAMPLE);
+    }, in.sh != nullptr);
+    GM_CHECK_LAUNCH();
+    SortPlan guess;
+    int rc = read_plan(ACC_SAMPLE, &guess);
+    if (rc || (rc = count(guess.first_digits(), ws.counts, true, guess.sq)) || (rc = read_plan(ACC_EXACT, &plan))) return rc;
+    *counted = guess.first_digits() == plan.first_digits() && guess.sq == plan.sq;
+    if (!*counted) GM_HIP(hipMemsetAsync(ws.counts, 0, COUNTS_BYTES, s));
+    return GM_OK;
+  }
+  // every key equal: table order = input order
+  int copy_equal() {
+    if (in.sh) GM_HIP(hipMemcpyAsync(sh_out, in.sh, (size_t)n, hipMemcpyDeviceToDevice, s));
+    GM_HIP(hipMemcpyAsync(bin_out, in.bin, (size_t)n * 2, hipMemcpyDeviceToDevice, s));
+    GM_HIP(hipMemcpyAsync(z_out, in.z, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(k_widen_perm, dim3((unsigned)std::min<int64_t>(4096, (n + STPB - 1) / STPB)), dim3(STPB), 0, s, n,
                        perm_out);
     GM_CHECK_LAUNCH();
     ctx->sort_last = 0;
     return GM_OK;
   }
-  // the sample's plan holds when the exact bits give the same first digits; else count again
-  bool counted = guess.first_digits() == plan.first_digits() && guess.sq == plan.sq;
-  if (!counted) GM_HIP(hipMemsetAsync(counts, 0, counts_bytes, s));
-  const bool prefix_mode = plan.prefix;
-  const int npre = plan.npre, pw = plan.pw;
-  const int* pofs = plan.pofs;
-  // digit passes at bit offsets `offs` (LSD order) from the caller's columns, tags tag0 + 1...; the
-  // last pass lands in the user outputs when `to_user_last`, else in records (*last_rec)
-  const uint4* last_rec = nullptr;
-  auto passes = [&](const std::vector<int>& offs, int w, bool to_user_last, int tag0) -> int {
+  // Digit passes of width w at bit offsets `offs` (LSD order) from the caller's columns, under tags tag0 + 1...;
+  // the last one lands in the user columns when `to_user`, else in records (*last, when asked for).  `counted`:
+  // the digits' counts are already at counts[tag0 * NB_MAX] (make_plan); else one read counts them first.
+  int digit_passes(const std::vector<int>& offs, int w, bool to_user, int tag0, bool counted, const uint4** last) {
     const int np = (int)offs.size();
-    DigitOffs o{};
-    o.np = np;
-    for (int k = 0; k < np; ++k) { o.off[k] = offs[k]; o.w[k] = w; }
-    uint32_t* cnt = counts + (size_t)tag0 * NB_MAX;
-    if (!counted) {
-      if (sh) hipLaunchKernelGGL((k_sort_count<true, false>), dim3(cgrid), dim3(CT), 0, s, in, n, o, cnt, user_wide, nullptr, plan.sq);
-      else hipLaunchKernelGGL((k_sort_count<false, false>), dim3(cgrid), dim3(CT), 0, s, in, n, o, cnt, user_wide, nullptr, 16);
-      if (hipGetLastError() != hipSuccess) return hip_fail(hipErrorLaunchFailure, "k_sort_count");
-    }
-    counted = false;   // a later call (the fallback) counts its own digits
-    for (int k = 0; k < np; ++k) {
-      PassArgs a{};
-      a.in = in;
-      a.rec_in = k > 0 ? rec[(k - 1) & 1] : nullptr;
-      a.sh_out = shard_out; a.bin_out = (uint16_t*)bin_out; a.z_out = (uint64_t*)z_out; a.perm_out = perm_out;
-      a.rec_out = rec[k & 1];
-      a.n = n; a.off = offs[k]; a.w = w; a.tag = (uint32_t)(tag0 + k + 1);
-      a.counts = cnt + (size_t)k * NB_MAX;
-      a.status = status;
-      a.ctr = ctr + tag0 + k;
-      a.vec = user_vec;
-      a.sq = plan.sq; a.binhi = plan.binhi;
-      const bool first = k == 0, user = to_user_last && k == np - 1;
-      void (*kern)(PassArgs) =
-          sh ? (first ? (user ? k_sort_pass<false, true, true> : k_sort_pass<false, false, true>)
-                      : (user ? k_sort_pass<true, true, true> : k_sort_pass<true, false, true>))
-             : (first ? (user ? k_sort_pass<false, true, false> : k_sort_pass<false, false, false>)
-                      : (user ? k_sort_pass<true, true, false> : k_sort_pass<true, false, false>));
-      hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(PT), 0, s, a);
-      if (hipGetLastError() != hipSuccess) return hip_fail(hipErrorLaunchFailure, "k_sort_pass");
-      last_rec = rec[k & 1];
-    }
-    return GM_OK;
-  };
-  if (prefix_mode) {
-    int rc = passes(plan.first_offs(), pw, false, 0);
+    uint32_t* cnt = ws.counts + (size_t)tag0 * NB_MAX;
+    const int rc = counted ? GM_OK : count(digit_offs(offs, w), cnt, false, plan.sq);
     if (rc) return rc;
-    const int4 po = make_int4(pofs[0], pofs[1], pofs[2], pofs[3]);
+    // aligned caller columns: the first pass then loads a full tile's rows unconditionally
+    const int vec = aligned_to<16>(in.z) && aligned_to<4>(in.bin) && aligned_to<2>(in.sh);
+    for (int k = 0; k < np; ++k) {   // pass k reads what pass k - 1 wrote; PassArgs in its declared order
+      const PassArgs a{in, k > 0 ? ws.rec[(k - 1) & 1] : nullptr, sh_out, bin_out, z_out, perm_out, ws.rec[k & 1], n,
+                       offs[k], w, (uint32_t)(tag0 + k + 1), cnt + (size_t)k * NB_MAX, ws.status, ws.ctr + tag0 + k, vec,
+                       plan.sq, plan.binhi};
+      with_flags([&](auto IN_REC, auto OUT_USER, auto SH) {
+        hipLaunchKernelGGL((k_sort_pass<IN_REC(), OUT_USER(), SH()>), dim3((unsigned)((n + PTILE - 1) / PTILE)), dim3(PT), 0,
+                           s, a);
+      }, k > 0, to_user && k == np - 1, in.sh != nullptr);
+      GM_CHECK_LAUNCH();
+    }
+    if (last) *last = ws.rec[(np - 1) & 1];
+    return GM_OK;
+  }
+  // The prefix passes, then every run of equal prefixes ranked in LDS into the user columns.  *done: the
+  // table is sorted; else a run was longer than RUN_MAX and the byte passes redo the sort.
+  int prefix_attempt(bool counted, bool* done) {
+    const uint4* last = nullptr;
+    const int rc = digit_passes(plan.first_offs(), plan.pw, false, 0, counted, &last);
+    if (rc) return rc;
+    const int4 po = make_int4(plan.pofs[0], plan.pofs[1], plan.pofs[2], plan.pofs[3]);
     const int lgrid = resident_blocks((const void*)k_sort_local<false>, ctx->device, LT, 2);
-    const int64_t nbound = (n + LSTEP - 1) / LSTEP + 1;
-    hipLaunchKernelGGL(k_local_bounds, dim3((unsigned)((nbound + 3) / 4)), dim3(256), 0, s, last_rec, n, po, pw, lbounds,
-                       (uint32_t*)(acc + 4));
-    if (sh)
-      hipLaunchKernelGGL(k_sort_local<true>, dim3(lgrid), dim3(LT), 0, s, last_rec, shard_out, (uint16_t*)bin_out,
-                         (uint64_t*)z_out, perm_out, n, po, pw, (uint32_t*)(acc + 4), lbounds, plan.sq, plan.binhi);
-    else
-      hipLaunchKernelGGL(k_sort_local<false>, dim3(lgrid), dim3(LT), 0, s, last_rec, nullptr, (uint16_t*)bin_out,
-                         (uint64_t*)z_out, perm_out, n, po, pw, (uint32_t*)(acc + 4), lbounds, plan.sq, plan.binhi);
+    const int64_t nbound = (n + LSTEP - 1) / LSTEP + 1;   // as SortWs carves lbounds
+    uint32_t* d_flag = (uint32_t*)(acc + ACC_FLAG);
+    hipLaunchKernelGGL(k_local_bounds, dim3((unsigned)((nbound + 3) / 4)), dim3(256), 0, s, last, n, po, plan.pw,
+                       ws.lbounds, d_flag);
+    with_flags([&](auto SH) {
+      hipLaunchKernelGGL(k_sort_local<SH()>, dim3(lgrid), dim3(LT), 0, s, last, sh_out, bin_out, z_out, perm_out, n, po,
+                         plan.pw, d_flag, ws.lbounds, plan.sq, plan.binhi);
+    }, in.sh != nullptr);
     GM_CHECK_LAUNCH();
     uint32_t flag = 0;
-    GM_HIP(hipMemcpyAsync(&flag, acc + 4, 4, hipMemcpyDeviceToHost, s));
+    GM_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
     GM_HIP(hipStreamSynchronize(s));
-    if (!flag) {
-      ctx->sort_last = 256 + npre;
-      return GM_OK;
-    }
-    // a run of equal prefixes longer than RUN_MAX: digit passes over every varying byte
+    *done = !flag;
+    if (*done) ctx->sort_last = 256 + plan.npre;
+    return GM_OK;
   }
-  ctx->sort_last = (int64_t)lsd.size() + (prefix_mode ? npre : 0);   // (a failed prefix attempt included)
-  return passes(lsd, 8, true, prefix_mode ? npre : 0);
-}
+};
 
-int gm_key_sample(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n, int32_t n_samples,
-                  uint64_t* key_hi, uint64_t* key_lo) {
-  if (!ctx || n < 0 || n > (int64_t)UINT32_MAX || n_samples < 0 || n_samples > 65536) return GM_E_INVALID;
-  if (n == 0 || n_samples == 0) return GM_OK;
-  if (!bin || !z || !key_hi || !key_lo) return GM_E_INVALID;
-  void* ws = nullptr;
-  int rc = ctx_workspace(ctx, WS_SCAN, (size_t)n_samples * 16, &ws);
-  if (rc) return rc;
-  const KeyCols in{shard, (const uint16_t*)bin, (const uint64_t*)z};
-  const dim3 g((unsigned)((n_samples + 255) / 256));
-  if (shard) hipLaunchKernelGGL(k_key_sample<true>, g, dim3(256), 0, ctx->stream, in, n, (int)n_samples, (uint64_t*)ws);
-  else hipLaunchKernelGGL(k_key_sample<false>, g, dim3(256), 0, ctx->stream, in, n, (int)n_samples, (uint64_t*)ws);
-  GM_CHECK_LAUNCH();
-  std::vector<uint64_t> h((size_t)n_samples * 2);
-  rc = copy_d2h(ctx, h.data(), ws, h.size() * 8);
-  if (rc) return rc;
-  for (int32_t i = 0; i < n_samples; ++i) {
-    key_hi[i] = h[2 * (size_t)i];
-    key_lo[i] = h[2 * (size_t)i + 1];
-  }
-  return GM_OK;
-}
+}  // namespace
 
-int gm_key_partition(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
-                     const uint64_t* split_hi, const uint64_t* split_lo, int32_t n_split, const int64_t* ids,
-                     int64_t id_base, uint8_t* shard_out, int16_t* bin_out, int64_t* z_out, int64_t* ids_out,
-                     uint32_t* rows_out, int64_t* dest_counts) {
-  if (!ctx || n < 0 || n > (int64_t)UINT32_MAX || n_split < 0 || n_split >= XMAX || !dest_counts) return GM_E_INVALID;
-  if (n_split > 0 && (!split_hi || !split_lo)) return GM_E_INVALID;
-  for (int32_t k = 0; k < n_split; ++k) {   // ascending splitters, keys of 24 bits + 64 bits
-    if (split_hi[k] >> 24) return set_error("gm_key_partition: splitter hi past 24 bits"), GM_E_INVALID;
-    if (k > 0 && (split_hi[k] < split_hi[k - 1] || (split_hi[k] == split_hi[k - 1] && split_lo[k] < split_lo[k - 1])))
-      return set_error("gm_key_partition: splitters not ascending"), GM_E_INVALID;
-  }
-  const int nd = n_split + 1;
-  for (int d = 0; d < nd; ++d) dest_counts[d] = 0;
+extern "C" int gm_sort_keys(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, const int64_t* z, int64_t n,
+                            uint8_t* shard_out, int16_t* bin_out, int64_t* z_out, int64_t* perm_out) {
+  if (!ctx || n < 0 || n > (int64_t)UINT32_MAX) return GM_E_INVALID;
   if (n == 0) return GM_OK;
-  if (!bin || !z || !bin_out || !z_out || ((shard == nullptr) != (shard_out == nullptr))) return GM_E_INVALID;
-  hipStream_t s = ctx->stream;
-  const int64_t ntiles = (n + XTILE - 1) / XTILE, ncnt = ntiles * nd;
-  // workspace: splitters | counts (u32, destination-major) | their scan (i64) | scan partials | totals
-  Carve c{16};
-  const size_t o_s = c.take((size_t)std::max(1, n_split) * 16), o_c = c.take((size_t)ncnt * 4), o_o = c.take((size_t)ncnt * 8),
-               o_p = c.take((size_t)scan_partials_len(ncnt) * 8), o_t = c.take((size_t)(nd + 1) * 8);
-  char* base = nullptr;
-  int rc = ctx_workspace(ctx, WS_SCAN, c.total, (void**)&base);
+  if (!z || !z_out || !perm_out || ((shard == nullptr) != (shard_out == nullptr)) ||
+      ((bin == nullptr) != (bin_out == nullptr)))
+    return GM_E_INVALID;
+  int rc = bin ? GM_OK : zero_bin(ctx, n, &bin, &bin_out);
   if (rc) return rc;
-  uint64_t* split = (uint64_t*)(base + o_s);
-  uint32_t* cnt = (uint32_t*)(base + o_c);
-  int64_t* offs = (int64_t*)(base + o_o);
-  int64_t* partials = (int64_t*)(base + o_p);
-  int64_t* dtot = (int64_t*)(base + o_t);   // [nd] destination totals, then the scan's grand total
-  if (n_split > 0) {
-    std::vector<uint64_t> hs((size_t)n_split * 2);
-    for (int32_t k = 0; k < n_split; ++k) { hs[2 * (size_t)k] = split_hi[k]; hs[2 * (size_t)k + 1] = split_lo[k]; }
-    rc = copy_h2d(ctx, split, hs.data(), hs.size() * 8);
-    if (rc) return rc;
+  SortCall c{ctx, ctx->stream, (unsigned long long*)ctx->d_scratch, KeyCols{shard, (const uint16_t*)bin, (const uint64_t*)z},
+             n, shard_out, (uint16_t*)bin_out, (uint64_t*)z_out, perm_out};
+  bool counted = false;
+  if ((rc = c.ws.take(ctx, n)) || (rc = c.make_plan(&counted))) return rc;
+  if (c.plan.lsd.empty()) return c.copy_equal();
+  int tag0 = 0;
+  if (c.plan.prefix) {
+    bool done = false;
+    if ((rc = c.prefix_attempt(counted, &done)) || done) return rc;
+    tag0 = c.plan.npre;   // flagged: the byte passes run under the tags after the attempt's ...
+    counted = false;      // ... and count their own digits
   }
-  int nbits = 0;
-  while ((1 << nbits) < nd) ++nbits;
-  const KeyCols in{shard, (const uint16_t*)bin, (const uint64_t*)z};
-  const dim3 grid((unsigned)ntiles);
-  if (shard) hipLaunchKernelGGL(k_part_count<true>, grid, dim3(XT), 0, s, in, n, split, n_split, nbits, cnt, ntiles);
-  else hipLaunchKernelGGL(k_part_count<false>, grid, dim3(XT), 0, s, in, n, split, n_split, nbits, cnt, ntiles);
-  GM_CHECK_LAUNCH();
-  launch_excl_scan<uint32_t, int64_t>(s, cnt, ncnt, offs, partials, dtot + nd);
-  hipLaunchKernelGGL(k_part_totals, dim3(1), dim3(XMAX), 0, s, offs, ntiles, nd, dtot + nd, dtot);
-  GM_CHECK_LAUNCH();
-  void (*kern)(KeyCols, int64_t, const uint64_t*, int, int, const int64_t*, int64_t, const int64_t*, int64_t, int64_t*,
-               uint32_t*, uint8_t*, uint16_t*, uint64_t*) =
-      shard ? (ids ? k_part_scatter<true, true> : k_part_scatter<true, false>)
-            : (ids ? k_part_scatter<false, true> : k_part_scatter<false, false>);
-  hipLaunchKernelGGL(kern, grid, dim3(XT), 0, s, in, n, split, n_split, nbits, offs, ntiles, ids, id_base, ids_out, rows_out,
-                     shard_out, (uint16_t*)bin_out, (uint64_t*)z_out);
-  GM_CHECK_LAUNCH();
-  return copy_d2h(ctx, dest_counts, dtot, (size_t)nd * 8);
+  ctx->sort_last = (int64_t)c.plan.lsd.size() + tag0;   // (a failed prefix attempt included)
+  return c.digit_passes(c.plan.lsd, 8, true, tag0, counted, nullptr);
 }
-
-}  // extern "C"

@@ -17,6 +17,12 @@ struct DigitOffs {
   int w[NPASS];
   int np;
 };
+inline DigitOffs digit_offs(const std::vector<int>& offs, int w) {   // digits of one width at `offs`
+  DigitOffs o{};
+  o.np = (int)offs.size();
+  for (int k = 0; k < o.np; ++k) { o.off[k] = offs[k]; o.w[k] = w; }
+  return o;
+}
 
 // The digits of one sort, from the OR / AND of the keys: `lsd` = every byte on which some keys differ
 // (LSD order); prefix mode = npre digits of pw <= 9 bits, each ending at the highest varying bit below
@@ -34,13 +40,7 @@ struct SortPlan {
     std::reverse(o.begin(), o.end());
     return o;
   }
-  DigitOffs first_digits() const {
-    DigitOffs o{};
-    const std::vector<int> f = first_offs();
-    o.np = (int)f.size();
-    for (int k = 0; k < o.np; ++k) { o.off[k] = f[k]; o.w[k] = prefix ? pw : 8; }
-    return o;
-  }
+  DigitOffs first_digits() const { return digit_offs(first_offs(), prefix ? pw : 8); }
 };
 inline bool operator==(const DigitOffs& a, const DigitOffs& b) {
   if (a.np != b.np) return false;

@@ -3,7 +3,10 @@
 perm a permutation that maps the output back to the input.  For A/B runs of library builds
 (GEOMESA_HIP_LIB) in one GPU call.
 
-    python tools/sort_probe.py [rows] [sharded]
+    python tools/sort_probe.py [rows] [sharded] [sort mode]
+
+`sort mode` sets GM_PARAM_SORT_MODE (include/geomesa_hip.h): 1 times the 8-bit digit passes over every
+varying byte, the only path on which k_sort_pass writes the user columns.
 """
 import os
 import sys
@@ -16,8 +19,10 @@ from geomesa_amd import _lib  # noqa: E402
 from geomesa_amd.curve import Z3SFC  # noqa: E402
 
 
-def main(n=250_000_000, sharded=False):
+def main(n=250_000_000, sharded=False, sort_mode=None):
     ctx = _lib.context()
+    if sort_mode is not None:
+        ctx.set_param(_lib.GM_PARAM_SORT_MODE, sort_mode)
     dev = torch.device("cuda", ctx.device)
     g = torch.Generator(device=dev).manual_seed(7)
     x = torch.rand(n, device=dev, generator=g, dtype=torch.float64) * 360 - 180
@@ -55,9 +60,10 @@ def main(n=250_000_000, sharded=False):
     ok = ok and bool(torch.equal(torch.sort(perm).values, torch.arange(n, device=dev)))
     if sharded:
         ok = ok and bool(torch.equal(osh, sh[perm]))
-    print("sort %d rows%s: best %.2f ms, mean %.2f ms, ok=%s" % (n, " sharded" if sharded else "", min(ts),
-                                                               sum(ts) / len(ts), ok), flush=True)
+    what = (" sharded" if sharded else "") + (" mode %d" % sort_mode if sort_mode is not None else "")
+    print("sort %d rows%s: best %.2f ms, mean %.2f ms, ok=%s" % (n, what, min(ts), sum(ts) / len(ts), ok), flush=True)
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 250_000_000, len(sys.argv) > 2 and sys.argv[2] == "1")
+    main(int(sys.argv[1]) if len(sys.argv) > 1 else 250_000_000, len(sys.argv) > 2 and sys.argv[2] == "1",
+         int(sys.argv[3]) if len(sys.argv) > 3 else None)
