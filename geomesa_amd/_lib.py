@@ -120,6 +120,17 @@ class Cms(ctypes.Structure):
                 ("hash_a", ctypes.c_int64 * GM_CMS_MAX_DEPTH)]
 
 
+GM_HIST_MAX_SEGMENTS = 256
+GM_HIST_LDS_BINS = 16384
+
+
+class HistState(ctypes.Structure):
+    """gm_hist_state: a Histogram's binding (GM_ATTR_*), length and bounds -- lo / hi for the whole-number
+    bindings, flo / fhi for float and double."""
+    _fields_ = [("type", ctypes.c_int32), ("length", ctypes.c_int32), ("lo", ctypes.c_int64),
+                ("hi", ctypes.c_int64), ("flo", ctypes.c_double), ("fhi", ctypes.c_double)]
+
+
 class BinOpts(ctypes.Structure):
     """gm_bin_opts: sort (0 scan order, 1 by BinSorter.compare) and the axis order (0 LonLat, 1 LatLon)."""
     _fields_ = [("sort", ctypes.c_int32), ("lat_lon", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
@@ -226,6 +237,13 @@ SIGNATURES = {
     "gm_frequency_attr": (cint, [vp, vp, vp, i64, vp, vp, i64, cint, cint, vp, vp, vp, vp]),
     "gm_frequency_points": (cint, [vp, vp, vp, vp, i64, vp, vp, i64, cint, cint, vp, vp, vp, vp]),
     "gm_cms_estimate": (cint, [vp, vp, vp, vp, vp, i64, vp]),
+    "gm_minmax_attr": (cint, [vp, vp, i64, vp, vp, i64, vp, vp, vp]),
+    "gm_histogram_attr": (cint, [vp, vp, i64, vp, vp, i64, cint, cint, vp, vp, vp]),
+    "gm_hist_index_of": (cint, [vp, vp, i64, vp]),
+    "gm_hist_bin_bounds": (cint, [vp, i32, vp]),
+    "gm_hist_median": (cint, [vp, i32, vp, vp]),
+    "gm_hist_copy_into": (cint, [vp, vp, vp, vp]),
+    "gm_hist_merge": (cint, [vp, vp, vp, vp]),
     "gm_gen_points": (cint, [vp, ctypes.c_uint64, i64, i64, d, d, d, d, i64, i64, vp, vp, vp]),
 }
 

@@ -732,5 +732,494 @@ class Z3Frequency(_SketchMap):
                 self.period == other.period and self.precision == other.precision and self._same_sketches(other))
 
 
+# ---------------------------------------------------------------------- Histogram, MinMax, Count
+_NO_BINDING = ("%s over a %s attribute is not implemented: a String bins base-36 prefixes and a Geometry the Z2 "
+               "key of its centroid, their expansion takes a component-wise minimum rather than an order on the "
+               "binned value, and their cardinality hashes toString")
+_LONG_MAX, _LONG_MIN = (1 << 63) - 1, -(1 << 63)
+
+
+def _order_key(v):
+    """Double.compareTo's order as a signed 64-bit key (include/geomesa_hip.h): its own inverse."""
+    b = int(np.float64(v).view(np.int64)) if v == v else 0x7FF8000000000000
+    return b ^ ((b >> 63) & _LONG_MAX)
+
+
+def _key_value(k):
+    return float(np.int64(k ^ ((k >> 63) & _LONG_MAX)).view(np.float64))
+
+
+def _attr_binding(what, binding):
+    if binding is None:
+        return None
+    binding = binding.lower()
+    if binding in ("string", "geometry"):
+        raise NotImplementedError(_NO_BINDING % (what, binding.capitalize()))
+    if binding not in _BINDINGS:
+        raise ValueError("no %s for class binding %s" % (what, binding))
+    return binding
+
+
+class _AttrStat:
+    """What Histogram and MinMax share: the binding, the device and the column / selection plumbing."""
+
+    def _init_attr(self, what, attribute, binding, device):
+        self.attribute = attribute
+        self.binding = _attr_binding(what, binding)
+        self._what, self._device = what, device
+        self.bad_ids = 0   # ids outside [0, n)
+
+    def _dev(self):
+        torch = _torch()
+        if self._device == "cpu":   # a host-only stat: merges and reads, no observe
+            return torch.device("cpu")
+        return torch.device("cuda", _lib.context(self._device).device)
+
+    def _column(self, values):
+        """(values as a device column of the binding's dtype, its gm_attr_column)."""
+        torch = _torch()
+        if not isinstance(values, torch.Tensor):
+            values = np.asarray(values)
+            if values.dtype.kind in "USO":
+                raise NotImplementedError(_NO_BINDING % (self._what, "String"))
+        if self.binding is None:
+            name = str(values.dtype).replace("torch.", "")
+            self.binding = _DTYPE_BINDING.get(name) or ("long" if "int" in name else "double")
+            self._bound()
+        dt = _BINDINGS[self.binding][1]
+        if isinstance(values, torch.Tensor):
+            v = values.to(self._dev()).to(getattr(torch, np.dtype(dt).name)).contiguous()
+        else:
+            v = torch.from_numpy(np.ascontiguousarray(values, dt).copy()).to(self._dev())
+        n = v.numel()
+        return v, _lib.AttrColumn(_BINDINGS[self.binding][0], 0, v.data_ptr() if n else None, None, None, 0)
+
+    def _bound(self):
+        pass
+
+
+class Histogram(_AttrStat):
+    """Stat.Histogram(attribute, length, lower, upper) (Histogram.scala:35-178) over attribute columns of the
+    bindings "int", "long", "date" (epoch ms), "float" and "double"; None takes the binding from the first
+    observed column's dtype.  String and Geometry raise NotImplementedError.
+
+    The result depends on the order of the rows, as the reference's does: observe takes them in ascending row
+    order, or in the order of ids.  The counts live on the device; .expansions counts the expandBins calls,
+    .bad_ids the ids outside [0, n).  device="cpu" gives a host-only stat for merging and reading."""
+
+    def __init__(self, attribute, length, bounds, binding=None, device=None):
+        self._init_attr("Histogram", attribute, binding, device)
+        self._length, self._bounds0 = int(length), (bounds[0], bounds[1])
+        self._state = None
+        self.counts = None    # int64 [length]
+        self.expansions = 0
+        self.path = 0         # gm_histogram_attr's path: 0 automatic, 1 LDS counters, 2 device atomics
+        if self._length < 1:
+            raise ValueError("length must be at least 1")
+        if self.binding is not None:
+            self._bound()
+
+    # ------------------------------------------------------------------ state
+    def _bound(self):
+        self._state = self._make_state(self._length, self._bounds0)
+        self.counts = _torch().zeros(self._length, dtype=_torch().int64, device=self._dev())
+
+    def _make_state(self, length, bounds):
+        lo, hi = bounds
+        if self.binding in ("int", "long", "date"):
+            st = _lib.HistState(_BINDINGS[self.binding][0], length, int(lo), int(hi), 0.0, 0.0)
+        else:
+            dt = _BINDINGS[self.binding][1]
+            st = _lib.HistState(_BINDINGS[self.binding][0], length, 0, 0, float(dt(lo)), float(dt(hi)))
+        if not self._lo_hi(st)[0] < self._lo_hi(st)[1]:
+            raise ValueError("Upper bound must be greater than lower bound: lower='%s' upper='%s'" % (lo, hi))
+        return st
+
+    def _lo_hi(self, st):
+        if self.binding in ("int", "long", "date"):
+            return int(st.lo), int(st.hi)
+        return float(st.flo), float(st.fhi)
+
+    def _need(self):
+        if self._state is None:
+            raise ValueError("the attribute's binding is not known before the first observe")
+        return self._state
+
+    def _new(self, length=None, bounds=None):
+        return Histogram(self.attribute, length or self.length, bounds or self.bounds, self.binding, self._device)
+
+    @property
+    def length(self):
+        return self._length if self._state is None else int(self._state.length)
+
+    @property
+    def bounds(self):
+        return self._bounds0 if self._state is None else self._lo_hi(self._state)
+
+    # ------------------------------------------------------------------ observe
+    def _apply(self, values, mask, ids, sign):
+        torch = _torch()
+        v, col = self._column(values)
+        n = v.numel()
+        mask, ids, n_ids = _selection(n, mask, ids, self._dev())
+        tally = torch.zeros(3, dtype=torch.int64, device=self._dev())
+        ctx = _lib.context(self._device)
+        check(ctx.lib.gm_histogram_attr(ctx.handle, ctypes.byref(col), n, ptr(mask), ptr(ids), n_ids, sign, self.path,
+                                        ctypes.byref(self._state), ptr(self.counts), ptr(tally)), "gm_histogram_attr")
+        t = tally.cpu().tolist()
+        self.expansions += int(t[1])
+        self.bad_ids += int(t[2])
+        return self
+
+    def observe(self, values, mask=None, ids=None):
+        """Histogram.observe (Histogram.scala:74-89) for a batch of attribute values; mask / ids: the rows a scan
+        or a table query kept, as Frequency.observe takes them."""
+        return self._apply(values, mask, ids, 1)
+
+    def unobserve(self, values, mask=None, ids=None):
+        """Histogram.unobserve (Histogram.scala:91-106)."""
+        return self._apply(values, mask, ids, -1)
+
+    # ------------------------------------------------------------------ reads
+    def _host_counts(self):
+        return np.ascontiguousarray(self.counts.cpu().numpy())
+
+    def count(self, i):
+        return int(self.counts[i])
+
+    def index_of(self, value):
+        """indexOf (BinnedArray.scala:195-203, :293-299, :327-333); an int for a scalar, else an int32 array."""
+        st = self._need()
+        v = np.ascontiguousarray(np.atleast_1d(value), _BINDINGS[self.binding][1])
+        out = np.zeros(v.size, np.int32)
+        check(_lib.load().gm_hist_index_of(ctypes.byref(st), v.ctypes.data, v.size, out.ctypes.data), "gm_hist_index_of")
+        return int(out[0]) if np.ndim(value) == 0 else out
+
+    def direct_index(self, value):
+        """directIndex(value: Long): the whole-number binnings' indexOf; -1 for float and double."""
+        if self.binding in ("float", "double"):
+            return -1
+        return self.index_of(value)
+
+    def bin_bounds(self, i):
+        """bounds(i) (BinnedArray.scala:213-223, :308-313, :342-347)."""
+        out = _lib.HistState()
+        check(_lib.load().gm_hist_bin_bounds(ctypes.byref(self._need()), int(i), ctypes.byref(out)), "gm_hist_bin_bounds")
+        return self._lo_hi(out)
+
+    def median_value(self, i):
+        """medianValue(i) (BinnedArray.scala:205-211, :301-306, :335-340)."""
+        iv, fv = ctypes.c_int64(), ctypes.c_double()
+        check(_lib.load().gm_hist_median(ctypes.byref(self._need()), int(i), ctypes.byref(iv), ctypes.byref(fv)),
+              "gm_hist_median")
+        return int(iv.value) if self.binding in ("int", "long", "date") else float(fv.value)
+
+    def is_empty(self):
+        return self.counts is None or not bool((self.counts != 0).any())
+
+    def clear(self):
+        if self.counts is not None:
+            self.counts.zero_()
+
+    # ------------------------------------------------------------------ merges
+    def _same_shape(self, other):
+        return self.length == other.length and self.bounds == other.bounds
+
+    def _set(self, st, counts):
+        self._state = st
+        self.counts = _torch().from_numpy(np.ascontiguousarray(counts[:st.length], np.int64).copy()).to(self._dev())
+
+    def _adopt(self, other):
+        if self.binding is None:
+            self.binding = other.binding
+            self._bound()
+        if other.binding != self.binding:
+            raise ValueError("cannot add a %s histogram to a %s one" % (other.binding, self.binding))
+
+    def __iadd__(self, other):
+        """+= (Histogram.scala:123-154): equal shapes add bin by bin; otherwise the bounds become the union of
+        the two actual bounds, the length the greater one, and both are copied in by copyInto."""
+        if other._state is None:
+            return self
+        self._adopt(other)
+        if self._same_shape(other):
+            self.counts += other.counts.to(self.counts.device)
+            return self
+        a = self._host_counts()
+        b = other._host_counts()
+        a = np.concatenate([a, np.zeros(max(0, other.length - self.length), np.int64)])
+        st = _lib.HistState.from_buffer_copy(self._state)
+        check(_lib.load().gm_hist_merge(ctypes.byref(st), a.ctypes.data, ctypes.byref(other._state), b.ctypes.data),
+              "gm_hist_merge")
+        self._set(st, a)
+        return self
+
+    def __add__(self, other):
+        out = self._new()
+        out += self
+        out += other
+        return out
+
+    def add_counts_from(self, other):
+        """addCountsFrom (Histogram.scala:66-72): as += but this histogram keeps its bounds and length."""
+        self._adopt(other)
+        if self._same_shape(other):
+            self.counts += other.counts.to(self.counts.device)
+            return self
+        a = self._host_counts()
+        b = other._host_counts()
+        check(_lib.load().gm_hist_copy_into(ctypes.byref(self._state), a.ctypes.data, ctypes.byref(other._state),
+                                            b.ctypes.data), "gm_hist_copy_into")
+        self._set(self._state, a)
+        return self
+
+    def all_reduce(self, pg):
+        """`+=` with every other rank's histogram over the process group.  When every rank has the same bounds
+        and length the counts add bin by bin (one all-reduce); otherwise the histograms are gathered and folded
+        with += IN RANK ORDER, rank 0 first -- += is not associative, so the order is part of the result, and
+        every rank computes the same one."""
+        if pg is None:
+            return self
+        from .shard import _device_of
+        torch = _torch()
+        mine = (self.binding, self.length, self.bounds) if self._state is not None else None
+        shapes = [None] * pg.get_world_size()
+        pg.all_gather_object(shapes, mine)
+        if all(s is not None and s == shapes[0] for s in shapes):
+            c = self.counts.to(_device_of(pg)).contiguous()
+            pg.all_reduce(c, op=pg.ReduceOp.SUM)
+            self.counts = c.to(self._dev()).contiguous()
+            return self
+        parts = [None] * len(shapes)
+        pg.all_gather_object(parts, None if mine is None else self._host_counts().tolist())
+        total = None
+        for s, c in zip(shapes, parts):
+            if s is None:
+                continue
+            h = Histogram(self.attribute, s[1], s[2], s[0], self._device)
+            h.counts = torch.tensor(c, dtype=torch.int64, device=self._dev())
+            if total is None:
+                total = h
+            else:
+                total += h
+        if total is not None:
+            self.binding, self._state, self.counts = total.binding, total._state, total.counts
+        return self
+
+    def to_json_object(self):
+        """toJsonObject (Histogram.scala:156-166)."""
+        lo, hi = self.bounds
+        c = self._host_counts()
+        bins = []
+        for i in range(self.length):
+            b = self.bin_bounds(i)
+            bins.append({"index": i, "lower-bound": b[0], "upper-bound": b[1], "count": int(c[i])})
+        return {"lower-bound": lo, "upper-bound": hi, "bins": bins}
+
+    def is_equivalent(self, other):
+        """isEquivalent (Histogram.scala:172-177)."""
+        return (isinstance(other, Histogram) and self.attribute == other.attribute and self.bounds == other.bounds and
+                np.array_equal(self._host_counts(), other._host_counts()))
+
+
+class MinMax(_AttrStat):
+    """Stat.MinMax(attribute) (MinMax.scala:29-114): the bounds by compareTo -- for float and double the total
+    order with -0.0 < 0.0 and NaN above everything -- and a HyperLogLog(10) cardinality whose hash is the
+    header's restated MurmurHash (parity unpinned).  The cardinality of a date attribute hashes Date.toString
+    and raises NotImplementedError; its min and max work.  A NaN comes back as the canonical NaN."""
+
+    def __init__(self, attribute, binding=None, device=None):
+        self._init_attr("MinMax", attribute, binding, device)
+        self._slots = None      # int64 [2] on the device: {minValue, maxValue} as order keys
+        self.registers = None   # int32 [1024]
+        if self.binding is not None:
+            self._bound()
+
+    def _defaults(self):
+        """(defaults.max, defaults.min) as slots (MinMax.scala:159-182)."""
+        if self.binding == "int":
+            return (1 << 31) - 1, -(1 << 31)
+        if self.binding in ("long", "date"):
+            return _LONG_MAX, _LONG_MIN
+        big = float(np.finfo(_BINDINGS[self.binding][1]).max)
+        return _order_key(big), _order_key(-big)
+
+    def _bound(self):
+        torch = _torch()
+        self._slots = torch.tensor(self._defaults(), dtype=torch.int64, device=self._dev())
+        if self.binding != "date":
+            self.registers = torch.zeros(1024, dtype=torch.int32, device=self._dev())
+
+    def _new(self):
+        return MinMax(self.attribute, self.binding, self._device)
+
+    def observe(self, values, mask=None, ids=None):
+        """MinMax.observe (MinMax.scala:51-62) for a batch of attribute values; stream-ordered."""
+        torch = _torch()
+        v, col = self._column(values)
+        n = v.numel()
+        mask, ids, n_ids = _selection(n, mask, ids, self._dev())
+        tally = torch.zeros(3, dtype=torch.int64, device=self._dev())
+        ctx = _lib.context(self._device)
+        check(ctx.lib.gm_minmax_attr(ctx.handle, ctypes.byref(col), n, ptr(mask), ptr(ids), n_ids, ptr(self._slots),
+                                     ptr(self.registers), ptr(tally)), "gm_minmax_attr")
+        if ids is not None:
+            self.bad_ids += int(tally[2])
+        return self
+
+    def unobserve(self, values, mask=None, ids=None):
+        """MinMax.unobserve is a no-op (MinMax.scala:65)."""
+        return self
+
+    def _host_slots(self):
+        return [int(s) for s in self._slots.cpu().tolist()]
+
+    def _value(self, slot):
+        if self.binding in ("int", "long", "date"):
+            return slot
+        v = _key_value(slot)
+        return float(np.float32(v)) if self.binding == "float" else v
+
+    def is_empty(self):
+        """isEmpty: minValue == defaults.max, so a stat that saw only defaults.max reads as empty."""
+        return self._slots is None or self._host_slots()[0] == self._defaults()[0]
+
+    @property
+    def min(self):
+        s = self._host_slots()
+        return self._value(s[1] if self.is_empty() else s[0])
+
+    @property
+    def max(self):
+        s = self._host_slots()
+        return self._value(s[0] if self.is_empty() else s[1])
+
+    @property
+    def bounds(self):
+        return self.min, self.max
+
+    @property
+    def cardinality(self):
+        """HyperLogLog.cardinality (HyperLogLog.scala:109-131) of the registers, on the host."""
+        if self.binding == "date":
+            raise NotImplementedError("the cardinality of a date attribute hashes Date.toString, which is not restated")
+        if self.registers is None:
+            return 0
+        s, zeros = 0.0, 0.0
+        for r in self.registers.cpu().tolist():
+            s += 1.0 / (1 << r)
+            if r == 0:
+                zeros += 1
+        estimate = ((0.7213 / (1 + 1.079 / 1024)) * 1024 * 1024) * (1 / s)
+        if estimate <= (5.0 / 2.0) * 1024:
+            return int(java_round(np.float64(1024 * math.log(1024 / zeros))))
+        return int(java_round(np.float64(estimate)))
+
+    @property
+    def tuple(self):
+        return self.min, self.max, self.cardinality
+
+    def clear(self):
+        if self._slots is not None:
+            self._bound()
+
+    def __iadd__(self, other):
+        """+= (MinMax.scala:79-91)."""
+        if other._slots is None or other.is_empty():
+            return self
+        if self.binding is None:
+            self.binding = other.binding
+            self._bound()
+        torch = _torch()
+        o = other._slots.to(self._slots.device)
+        if self.is_empty():
+            self._slots = o.clone()
+        else:
+            self._slots = torch.stack([torch.minimum(self._slots[0], o[0]), torch.maximum(self._slots[1], o[1])])
+        if self.registers is not None and other.registers is not None:
+            self.registers = torch.maximum(self.registers, other.registers.to(self.registers.device))
+        return self
+
+    def __add__(self, other):
+        out = self._new()
+        out += self
+        out += other
+        return out
+
+    def all_reduce(self, pg):
+        """min, max and the register-wise maximum over the process group: order-free.  An empty rank sends the
+        defaults, which are the reductions' identities."""
+        if pg is None:
+            return self
+        from .shard import _device_of
+        if self._slots is None:
+            raise ValueError("the attribute's binding is not known before the first observe")
+        dev = _device_of(pg)
+        s = self._slots.to(dev)
+        mn, mx = s[0:1].clone(), s[1:2].clone()
+        pg.all_reduce(mn, op=pg.ReduceOp.MIN)
+        pg.all_reduce(mx, op=pg.ReduceOp.MAX)
+        self._slots = _torch().cat([mn, mx]).to(self._dev())
+        if self.registers is not None:
+            r = self.registers.to(dev).contiguous()
+            pg.all_reduce(r, op=pg.ReduceOp.MAX)
+            self.registers = r.to(self._dev())
+        return self
+
+    def to_json_object(self):
+        """toJsonObject (MinMax.scala:93-98): nulls and 0 when empty."""
+        if self.is_empty():
+            return {"min": None, "max": None, "cardinality": 0}
+        s = self._host_slots()
+        return {"min": self._value(s[0]), "max": self._value(s[1]),
+                "cardinality": None if self.binding == "date" else self.cardinality}
+
+    def is_equivalent(self, other):
+        """isEquivalent (MinMax.scala:108-113)."""
+        return (isinstance(other, MinMax) and self.attribute == other.attribute and self.binding == other.binding and
+                self._slots is not None and other._slots is not None and self._host_slots() == other._host_slots() and
+                (self.binding == "date" or self.cardinality == other.cardinality))
+
+
+class Count:
+    """Stat.Count() (CountStat.scala:18-46).  No kernel: every scan returns its match count, and observe takes
+    that number (a scan's n_match, a tally's rows observed)."""
+
+    def __init__(self, count=0):
+        self.count = int(count)
+
+    def observe(self, count=1):
+        self.count += int(count)
+        return self
+
+    def unobserve(self, count=1):
+        self.count -= int(count)
+        return self
+
+    def __iadd__(self, other):
+        self.count += other.count
+        return self
+
+    def __add__(self, other):
+        return Count(self.count + other.count)
+
+    def all_reduce(self, pg):
+        from .shard import all_reduce_scalar
+        self.count = int(all_reduce_scalar(pg, self.count, op="sum"))
+        return self
+
+    def to_json_object(self):
+        return {"count": self.count}
+
+    def is_empty(self):
+        return self.count == 0
+
+    def clear(self):
+        self.count = 0
+
+    def is_equivalent(self, other):
+        return isinstance(other, Count) and self.count == other.count
+
+
 __all__ = ["Z3Histogram", "long_binning_index", "MIN_Z", "MAX_Z", "Frequency", "Z3Frequency", "cms_shape",
-           "cms_hash_a", "frequency_mask", "java_round"]
+           "cms_hash_a", "frequency_mask", "java_round", "Histogram", "MinMax", "Count"]

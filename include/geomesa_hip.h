@@ -902,7 +902,7 @@ int gm_density_sparse(gm_ctx* ctx, const double* grid, int32_t width, int32_t he
 #define GM_ATTR_INT64 2
 #define GM_ATTR_FLOAT64 3
 #define GM_ATTR_UTF8 4      /* Arrow Utf8: int32 offsets [n + 1] + bytes */
-#define GM_ATTR_FLOAT32 5   /* gm_frequency_attr only; gm_bin_track / gm_bin_label reject it */
+#define GM_ATTR_FLOAT32 5   /* the stats scans (gm_frequency_attr, gm_histogram_attr, gm_minmax_attr); gm_bin_track / gm_bin_label reject it */
 typedef struct {
   int32_t type;              /* GM_ATTR_* */
   int32_t reserved;
@@ -1064,6 +1064,105 @@ int gm_frequency_points(gm_ctx* ctx, const double* x, const double* y, const gm_
    n < 0; the sketch and window errors above; keys or out NULL with n > 0; a misaligned pointer. */
 int gm_cms_estimate(gm_ctx* ctx, const gm_cms* cms, const int64_t* table, const int64_t* keys, const int16_t* bins,
                     int64_t n, int64_t* out);
+
+/* ------------------------------------------------------------------ Histogram / MinMax of an attribute */
+/* The two per-attribute stats the planner costs a strategy with: Histogram
+   (geomesa-utils/.../stats/Histogram.scala over BinnedArray.scala) and MinMax (.../stats/MinMax.scala with
+   clearspring/HyperLogLog.scala).  Bindings: Integer = GM_ATTR_INT32, Long and Date (epoch ms) =
+   GM_ATTR_INT64, Float = GM_ATTR_FLOAT32, Double = GM_ATTR_FLOAT64.  String and Geometry bindings are not
+   restated (GM_ATTR_UTF8 is GM_E_INVALID).  Nothing is fused (-ffp-contract=off) and every division is the
+   correctly rounded IEEE one, float32 included.
+
+   Binning (BinnedArray.scala:185-201, :284-350), `length` bins over the bounds [lo, hi], lo < hi:
+     whole numbers  binSize = (double)(hi - lo) / length, the Long difference wrapping;
+                    indexOf(v) = -1 when v < lo || v > hi, else i = d2i(floor((double)(v - lo) / binSize)), v - lo
+                    wrapping, d2i the JVM's saturating conversion (NaN -> 0);
+     float          the same in float32: binSize = (hi - lo) / (float)length, i = d2i(floor((double)((v - lo) /
+                    binSize)));
+     double         the same in FP64;
+     then i < 0 || i > length gives -1 and i == length gives length - 1.
+   A NaN passes both comparisons and floor(NaN) converts to 0: it counts in bin 0 and never expands.  An
+   infinity expands to an infinite bound, after which the quotients are NaN and land in bin 0; no special case.
+     bounds(i)      whole: lo' = lo + d2l(ceil(binSize * i)), hi' = max(lo', lo + d2l(floor(binSize * (i + 1)))),
+                    lo' <= lo gives lo and hi' >= hi gives hi (an Int binding truncates with toInt);
+                    float / double: (lo + binSize * i, lo + binSize * (i + 1)).
+     medianValue(i) whole: lo + Math.round(binSize / 2 + binSize * i), hi when that exceeds hi;
+                    float / double: lo + binSize / 2 + binSize * i.
+   observe (Histogram.scala:74-89): counts(indexOf(v)) += 1; when indexOf(v) is -1, expandBins (:226-232) first:
+   bounds (min(v, lo), max(v, hi)), the same length, copyInto(new, old), then add(v).  unobserve subtracts.
+   copyInto (:260-292): for every source bin with count > 0, lo = toIndex(bounds(i).min), hi =
+   toIndex(bounds(i).max), toIndex(x) = indexOf(x) in the target, or 0 / length - 1 for an x below / above it;
+   lo == hi adds the count there, else size = hi - lo + 1, every bin of lo..hi gets count / size and bin
+   lo + size / 2 gets count % size more (size <= 0 throws, and observe then drops the feature with a warning).
+   So a histogram depends on which rows came before each expansion: ORDER IS PART OF THE CONTRACT.  The rows
+   that expand are those whose indexOf under the running bounds is -1: a value below every earlier value and
+   lo, or above every earlier value and hi (and, once a Long span has wrapped, values the wrapped arithmetic
+   rejects).  gm_histogram_attr finds these records with a prefix-extrema scan, counts every row under the
+   bounds that held when the reference saw it, and replays the expansions on the host.
+
+   MinMax (MinMax.scala:51-62, :149-182): min and max by compareTo -- for Float and Double the total order
+   with -0.0 < 0.0 and NaN above +Infinity -- and a HyperLogLog(10) of the values.  A float or double travels
+   as the order key of its double: key = bits ^ ((bits >> 63) & INT64_MAX), its own inverse, every NaN first
+   made 0x7ff8000000000000; Float widens to double exactly, which keeps the order.
+   HyperLogLog (clearspring/HyperLogLog.scala:99-131, :168-178): 1,024 Int registers; for the 32-bit hash h
+   of a value, j = h >>> 22, r = numberOfLeadingZeros((h << 10) | 513) + 1 (the source's `1 << 9 + 1`
+   or-ed in whole), register[j] = max(register[j], r).  cardinality() sums 1.0 / (1 << register) in register
+   order, counts the zero registers, estimate = (0.7213 / (1 + 1.079 / 1024)) * 1024 * 1024 / sum; an estimate
+   <= 2.5 * 1024 gives Math.round(1024 * ln(1024 / zeros)), else Math.round(estimate).
+   The hash is com.clearspring.analytics.hash.MurmurHash.hash(Object), outside the reference tree: PARITY
+   UNPINNED, defined here as hashLong(key), key = the sign-extended Integer, the Long, doubleToRawLongBits,
+   or floatToRawIntBits sign-extended, in wrapping 32-bit arithmetic:
+     m = 0x5bd1e995; h = 0
+     k = (int)key * m;          k ^= k >>> 24;  h ^= k * m
+     k = (int)(key >> 32) * m;  k ^= k >>> 24;  h *= m;  h ^= k * m
+     h ^= h >>> 13;  h *= m;  h ^= h >>> 15
+   A Date's cardinality hashes Date.toString and is not restated. */
+typedef struct {
+  int32_t type;      /* GM_ATTR_INT32 / INT64 / FLOAT32 / FLOAT64 */
+  int32_t length;    /* bins, >= 1 */
+  int64_t lo, hi;    /* the bounds of a whole-number binding */
+  double flo, fhi;   /* the bounds of a float (exactly widened) or double binding */
+} gm_hist_state;
+#define GM_HIST_MAX_SEGMENTS 256   /* records one round of gm_histogram_attr replays */
+#define GM_HIST_LDS_BINS 16384     /* longest histogram the workgroup-private counters hold */
+
+/* MinMax.observe over the selected, non-null rows of an attribute column (selection exactly as
+   gm_frequency_attr: none, mask, or ids in the caller's order with repeats; a reduction, so order does not
+   matter).  minmax (device int64[2], in/out): {min, max}, a whole number as itself, a float / double as its
+   order key; the caller starts them at the binding's defaults.max / defaults.min.  registers (device
+   int32[1024], in/out) or NULL for no cardinality.  tally (device int64[3], accumulated): {rows observed,
+   unused, ids outside [0, n)}.  Stream-ordered, no readback.  GM_E_INVALID: a NULL ctx, col, minmax or
+   tally; GM_ATTR_UTF8 or an unknown type; values NULL with n > 0 or not naturally aligned; n < 0; the
+   selection errors; a misaligned output. */
+int gm_minmax_attr(gm_ctx* ctx, const gm_attr_column* col, int64_t n, const uint64_t* mask, const int64_t* ids,
+                   int64_t n_ids, int64_t* minmax, int32_t* registers, int64_t* tally);
+/* Histogram.observe (sign +1) / unobserve (sign -1) over the selected, non-null rows of an attribute column, in
+   selection order: ascending rows, or the order of ids.  state (host, in/out): the binding (col->type must
+   equal state->type), the length and the bounds, which come back expanded.  counts (device int64[length],
+   in/out).  tally (device int64[3], accumulated): {rows observed, expansions, ids outside [0, n)}.
+   path: 0 automatic, 1 workgroup-private uint32 counters in LDS (length <= GM_HIST_LDS_BINS), 2 device atomics;
+   the result never depends on it.  Works in rounds of at most GM_HIST_MAX_SEGMENTS records; a sorted column
+   is a record per row and stays correct and slow, as in the reference.  Synchronises the context stream: it
+   reads the record count back, and with records the counts.  GM_E_INVALID, with a gm_last_error text: a NULL
+   ctx, col, state, counts or tally; GM_ATTR_UTF8, an unknown type or one that differs from the state's;
+   length < 1; bounds with lo >= hi; sign other than +1 / -1; path outside 0..2, or path 1 with a longer
+   histogram; values NULL with n > 0 or not naturally aligned; n < 0; the selection errors; a misaligned
+   output. */
+int gm_histogram_attr(gm_ctx* ctx, const gm_attr_column* col, int64_t n, const uint64_t* mask, const int64_t* ids,
+                      int64_t n_ids, int sign, int path, gm_hist_state* state, int64_t* counts, int64_t* tally);
+/* The host half, no context and no GPU (all pointers host).  values: n values of the binding's type.
+   gm_hist_index_of: indexOf of each value into index[n].  gm_hist_bin_bounds / gm_hist_median: bounds(i) into
+   out's bounds fields (type and length copied) / medianValue(i) into *iv or *fv; 0 <= i <= length as the
+   reference allows.  gm_hist_copy_into: copyInto(to, from); GM_E_INVALID with to_counts untouched where the
+   reference throws.  gm_hist_merge: a += b (Histogram.scala:123-154, checkEndpoints / getActualBounds
+   :238-253); a_counts holds max(a->length, b->length) entries, a comes back with the merged bounds and
+   length.  GM_E_INVALID: NULL pointers, a bad state, differing types, an index out of range. */
+int gm_hist_index_of(const gm_hist_state* state, const void* values, int64_t n, int32_t* index);
+int gm_hist_bin_bounds(const gm_hist_state* state, int32_t i, gm_hist_state* out);
+int gm_hist_median(const gm_hist_state* state, int32_t i, int64_t* iv, double* fv);
+int gm_hist_copy_into(const gm_hist_state* to, int64_t* to_counts, const gm_hist_state* from,
+                      const int64_t* from_counts);
+int gm_hist_merge(gm_hist_state* a, int64_t* a_counts, const gm_hist_state* b, const int64_t* b_counts);
 
 /* ------------------------------------------------------------------ synthetic data (bench/tests) */
 /* SplitMix64 keyed by (seed, index): lon U[lon0,lon1), lat U[lat0,lat1), t_ms U[t0,t1).  Each of x, y and
