@@ -108,6 +108,20 @@ class AttrColumn(ctypes.Structure):
                 ("offsets", ctypes.c_void_p), ("validity", ctypes.c_void_p), ("validity_offset", ctypes.c_int64)]
 
 
+GM_ATTR_TIER_NONE, GM_ATTR_TIER_DATE, GM_ATTR_TIER_Z3 = 0, 1, 2
+
+
+class AttrRange(ctypes.Structure):
+    """gm_attr_range: an inclusive scan range of the attribute table's (shard, v, b, t) key."""
+    _fields_ = [("v_lo", ctypes.c_uint64), ("v_hi", ctypes.c_uint64), ("t_lo", ctypes.c_uint64),
+                ("t_hi", ctypes.c_uint64), ("b_lo", ctypes.c_uint16), ("b_hi", ctypes.c_uint16),
+                ("shard", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+# numpy view of gm_attr_range rows (40 B, the AttrRange layout)
+ATTR_RANGE_DTYPE = np.dtype([("v_lo", "<u8"), ("v_hi", "<u8"), ("t_lo", "<u8"), ("t_hi", "<u8"), ("b_lo", "<u2"),
+                             ("b_hi", "<u2"), ("shard", "u1"), ("reserved", "u1", (3,))])
+
 GM_CMS_MAX_DEPTH = 32
 
 
@@ -244,6 +258,10 @@ SIGNATURES = {
     "gm_hist_median": (cint, [vp, i32, vp, vp]),
     "gm_hist_copy_into": (cint, [vp, vp, vp, vp]),
     "gm_hist_merge": (cint, [vp, vp, vp, vp]),
+    "gm_attr_index_key": (cint, [vp, vp, i64, vp, vp, vp]),
+    "gm_attr_key_bytes": (cint, [vp, cint, vp, vp, cint, vp, vp, i64, vp]),
+    "gm_attr_sort": (cint, [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
+    "gm_attr_table_scan": (cint, [vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp]),
     "gm_gen_points": (cint, [vp, ctypes.c_uint64, i64, i64, d, d, d, d, i64, i64, vp, vp, vp]),
 }
 

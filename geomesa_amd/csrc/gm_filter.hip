@@ -301,42 +301,27 @@ __global__ __launch_bounds__(FTPB) void k_filter_rows_mask(const uint8_t* __rest
 // maps to a row interval by two binary searches; the intervals' rows are the candidates
 // (Accumulo/HBase scan), and Z3Filter.inBounds runs on each (RowFilterIterator.scala:52-66) in the
 // same mask -> block scan -> ordered compaction pipeline as the full scans.
-struct DevRange {
-  uint64_t z_lo, z_hi;
-  uint32_t kb_lo, kb_hi;   // shard << 16 | (uint16) bin
+// The Z tables' key: (shard << 16 | (uint16) bin, z), the byte order of [shard][bin BE16][z BE64].  The seek
+// itself (k_range_bounds, merge_ranges, seek_ranges) is gm_scan.hpp's, shared with the attribute table.
+struct ZKey {
+  uint64_t z;
+  uint32_t kb;   // shard << 16 | (uint16) bin
+  __host__ __device__ static bool lt(const ZKey& a, const ZKey& b) { return a.kb < b.kb || (a.kb == b.kb && a.z < b.z); }
+  static bool next(const ZKey& k, ZKey* out) {
+    *out = ZKey{k.z + 1, k.z == ~0ull ? k.kb + 1 : k.kb};
+    return !(k.z == ~0ull && k.kb == ~0u);
+  }
 };
-
-__device__ __forceinline__ bool key_lt(uint32_t ka, uint64_t za, uint32_t kb, uint64_t zb) {
-  return ka < kb || (ka == kb && za < zb);
-}
-
 // bin = null: a key space without a time bin (Z2 / XZ2: [shard][z BE64]), every row's bin reads as 0
-__device__ __forceinline__ uint32_t row_kb(const uint8_t* sh, const uint16_t* bin, int64_t i) {
-  return ((uint32_t)(sh ? sh[i] : 0) << 16) | (bin ? bin[i] : 0u);
-}
-
-// row interval of each range: [first row >= lo, first row > hi)
-__global__ __launch_bounds__(FTPB) void k_range_bounds(const uint8_t* __restrict__ sh, const uint16_t* __restrict__ bin,
-                                                       const uint64_t* __restrict__ z, int64_t n,
-                                                       const DevRange* __restrict__ rg, int64_t nr,
-                                                       int64_t* __restrict__ start, int64_t* __restrict__ len) {
-  const int64_t r = (int64_t)blockIdx.x * FTPB + threadIdx.x;
-  if (r >= nr) return;
-  const DevRange q = rg[r];
-  int64_t lo = 0, hi = n;  // lower_bound(lo key)
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (key_lt(row_kb(sh, bin, m), z[m], q.kb_lo, q.z_lo)) lo = m + 1; else hi = m;
+struct ZCols {
+  using Key = ZKey;
+  const uint8_t* sh;
+  const uint16_t* bin;
+  const uint64_t* z;
+  __device__ __forceinline__ ZKey at(int64_t i) const {
+    return ZKey{z[i], ((uint32_t)(sh ? sh[i] : 0) << 16) | (bin ? bin[i] : 0u)};
   }
-  const int64_t a = lo;
-  hi = n;  // upper_bound(hi key)
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (!key_lt(q.kb_hi, q.z_hi, row_kb(sh, bin, m), z[m])) lo = m + 1; else hi = m;
-  }
-  start[r] = a;
-  len[r] = lo - a;
-}
+};
 
 // in-place exclusive scan of int64 lengths (one block); total -> a[len]
 __global__ __launch_bounds__(1024) void k_scan_i64(int64_t* __restrict__ a, int64_t len) {
@@ -365,7 +350,6 @@ __global__ __launch_bounds__(1024) void k_scan_i64(int64_t* __restrict__ a, int6
 // XZ3IndexKeySpace.scala:247-250) over the caller's feature columns, reached through `rows` (table row ->
 // column row; not the id map k_cand_to_row applies): JTS Envelope.intersects with any query box
 // (inclusive), and FastDuring (exclusive, ms) on the dtg.
-enum : int { RF_NONE = 0, RF_Z3 = 1, RF_Z2 = 2 };
 struct FullFilter {
   const double *xmin, *ymin, *xmax, *ymax;   // feature envelopes (column order)
   const int64_t* t;                           // feature dtg (column order)
@@ -558,17 +542,6 @@ int finish_scan(gm_ctx* ctx, int64_t n, ScanBufs& b, int64_t* ids, int64_t ids_c
 
 }  // namespace gm
 
-namespace {
-
-// host mirror of the table's key order: (shard << 16 | bin as uint16, z as uint64)
-struct HostRange {
-  uint32_t kb_lo, kb_hi;
-  uint64_t z_lo, z_hi;
-};
-inline bool h_lt(uint32_t ka, uint64_t za, uint32_t kb, uint64_t zb) { return ka < kb || (ka == kb && za < zb); }
-
-}  // namespace
-
 extern "C" {
 
 int gm_z3filter_scan(gm_ctx* ctx, const uint8_t* filter_bytes, size_t filter_len, const int16_t* bin_ranges,
@@ -737,9 +710,7 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
     with_boxes.n_boxes = hq.n_parts;
     f = &with_boxes;
   }
-  const bool env = f->n_boxes > 0, dur = f->during != 0;
-  if (f->n_boxes < 0 || (env && (!f->boxes || !f->xmin || !f->ymin || !f->xmax || !f->ymax)) || (dur && !f->t_ms))
-    return GM_E_INVALID;
+  if (!full_filter_ok(f)) return GM_E_INVALID;
   // the row filter's descriptor: Z3Filter.deserializeFromBytes or Z2Filter's boxes
   std::vector<int32_t> desc;
   int rf = RF_NONE, nxy = 0;
@@ -759,52 +730,43 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
     rf = RF_Z2;
   }
   // the BatchScanner's view of the ranges: sorted, overlapping / adjacent ones merged
-  std::vector<HostRange> rs;
+  std::vector<SeekRange<ZKey>> rs;
   rs.reserve((size_t)n_ranges);
   for (int64_t i = 0; i < n_ranges; ++i) {
     const gm_key_range& r = ranges[i];
-    HostRange h{((uint32_t)r.shard << 16) | (uint16_t)r.bin_lo, ((uint32_t)r.shard << 16) | (uint16_t)r.bin_hi,
-                (uint64_t)r.z_lo, (uint64_t)r.z_hi};
-    if (h_lt(h.kb_hi, h.z_hi, h.kb_lo, h.z_lo)) continue;  // empty
-    rs.push_back(h);
+    rs.push_back(SeekRange<ZKey>{ZKey{(uint64_t)r.z_lo, ((uint32_t)r.shard << 16) | (uint16_t)r.bin_lo},
+                                 ZKey{(uint64_t)r.z_hi, ((uint32_t)r.shard << 16) | (uint16_t)r.bin_hi}});
   }
-  std::sort(rs.begin(), rs.end(), [](const HostRange& a, const HostRange& b) { return h_lt(a.kb_lo, a.z_lo, b.kb_lo, b.z_lo); });
-  std::vector<DevRange> dr;
-  for (const HostRange& h : rs) {
-    if (!dr.empty()) {
-      DevRange& last = dr.back();
-      // merge when h.lo <= last.hi + 1 in key order
-      const bool le = !h_lt(last.kb_hi, last.z_hi, h.kb_lo, h.z_lo) ||
-                      (last.z_hi != ~0ull && last.kb_hi == h.kb_lo && last.z_hi + 1 == h.z_lo) ||
-                      (last.z_hi == ~0ull && h.z_lo == 0 && last.kb_hi + 1 == h.kb_lo);
-      if (le) {
-        if (h_lt(last.kb_hi, last.z_hi, h.kb_hi, h.z_hi)) { last.kb_hi = h.kb_hi; last.z_hi = h.z_hi; }
-        continue;
-      }
-    }
-    dr.push_back(DevRange{h.z_lo, h.z_hi, h.kb_lo, h.kb_hi});
-  }
+  const std::vector<SeekRange<ZKey>> dr = merge_ranges(std::move(rs));
   const int64_t nr = (int64_t)dr.size();
-  if (n == 0 || nr == 0) {
-    if (n_match) *n_match = 0;
-    if (n_scanned) *n_scanned = 0;
-    if (n_envelope) *n_envelope = 0;
-    return GM_OK;
-  }
-  hipStream_t s = ctx->stream;
-  DevTemps tmp(s);
-  DevRange* d_rg = nullptr;
+  if (n == 0 || nr == 0) return no_candidates(n_match, n_scanned, n_envelope);
+  DevTemps tmp(ctx->stream);
   int64_t *start = nullptr, *coff = nullptr;
-  int rc = tmp.alloc_async((size_t)nr * sizeof(DevRange), &d_rg);
-  if (!rc) rc = tmp.alloc_async((size_t)nr * 8, &start);
-  if (!rc) rc = tmp.alloc_async((size_t)(nr + 1) * 8, &coff);
-  if (!rc) rc = copy_h2d(ctx, d_rg, dr.data(), (size_t)nr * sizeof(DevRange));
+  const int rc = seek_ranges(ctx, tmp, ZCols{shard, (const uint16_t*)bin, (const uint64_t*)z}, n, dr, &start, &coff);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_range_bounds, dim3((unsigned)((nr + FTPB - 1) / FTPB)), dim3(FTPB), 0, s, shard,
-                     (const uint16_t*)bin, (const uint64_t*)z, n, d_rg, nr, start, coff);
+  const RowFilter row_filter{rf, nxy, &desc, (const uint16_t*)bin, (const uint64_t*)z};
+  return scan_candidates(ctx, tmp, start, coff, nr, f, row_filter, geom, polys ? &hq : nullptr, perm, ids, ids_cap,
+                         n_match, n_scanned, n_envelope);
+}
+
+namespace gm {
+
+// The candidates of the seek's row intervals (start, and their lengths in coff) through the mask pass and
+// the compaction: what gm_table_scan, gm_table_scan_geom and gm_attr_table_scan share after their own seek.
+int scan_candidates(gm_ctx* ctx, DevTemps& tmp, const int64_t* start, int64_t* coff, int64_t nr,
+                    const gm_scan_filter* f, const RowFilter& row_filter, const gm_geom_column* geom,
+                    const polyq::HostQuery* hq, const int64_t* perm, int64_t* ids, int64_t ids_cap, int64_t* n_match,
+                    int64_t* n_scanned, int64_t* n_envelope) {
+  hipStream_t s = ctx->stream;
+  const bool env = f->n_boxes > 0, dur = f->during != 0, polys = hq != nullptr;
+  const std::vector<int32_t>& desc = *row_filter.words;
+  const uint16_t* bin = row_filter.bin;
+  const uint64_t* z = row_filter.z;
+  const int rf = row_filter.rf, nxy = row_filter.nxy;
+  int rc = GM_OK;
   hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, s, coff, nr);
   GM_CHECK_LAUNCH();
-  int64_t total = 0;   // the candidate count sizes the pass below (and dr is pageable: the wait covers its copy)
+  int64_t total = 0;   // the candidate count sizes the pass below (and the ranges are pageable: the wait covers their copy)
   if ((rc = read_i64(ctx, coff + nr, &total))) return rc;
   if (n_scanned) *n_scanned = total;
   int64_t nm = 0, ne = 0;
@@ -841,7 +803,7 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
         const GeomRefine gr{surv, ne, coff, start, nr, total, ff.rows, f->xmin, f->ymin, f->xmax, f->ymax, ff.boxes,
                             f->n_boxes, b.mask, b.counts};
         PolyQuery pq;
-        if (polys && (rc = upload_polys(ctx, tmp, hq, pq))) return rc;
+        if (polys && (rc = upload_polys(ctx, tmp, *hq, pq))) return rc;
         if ((rc = geom_refine(ctx, geom, gr, polys ? &pq : nullptr))) return rc;
       }
     }
@@ -859,6 +821,8 @@ static int table_scan(gm_ctx* ctx, const uint8_t* shard, const int16_t* bin, con
   if (ids && nm > ids_cap) return GM_E_CAPACITY;
   return GM_OK;
 }
+
+}  // namespace gm
 
 extern "C" {
 

@@ -1,12 +1,16 @@
 // gm_scan.hpp -- what the streaming scans share: the two mask-pass skeletons (pair_scan: two rows per
 // lane; row_scan: one), the device-wide exclusive scan with its count -> scan -> total helper
 // (CountScan), the row selection of the aggregating scans (RowSel, sel_row) and the mask -> block scan ->
-// ordered compaction pipeline of the filter scans (alloc_scan / finish_scan / end_scan).  Used by
-// gm_filter.hip, gm_geom_filter.hip, gm_pip_query.hip, gm_density.hip, gm_bin.hip and gm_freq.hip.
+// ordered compaction pipeline of the filter scans (alloc_scan / finish_scan / end_scan), and the seek and
+// candidate scan of the sorted tables (k_range_bounds, seek_ranges, scan_candidates).  Used by gm_filter.hip,
+// gm_geom_filter.hip, gm_pip_query.hip, gm_density.hip, gm_bin.hip, gm_freq.hip and gm_attr_table.hip.
 #pragma once
+
+#include <algorithm>
 
 #include "gm_internal.hpp"
 #include "gm_poly_query_host.hpp"
+#include "gm_seek.hpp"
 
 namespace gm {
 
@@ -315,6 +319,81 @@ __device__ __forceinline__ int64_t cand_row(const int64_t* __restrict__ coff, co
   const int64_t r = offset_slot(coff, nr, c);
   return start[r] + (c - coff[r]);
 }
+
+// ------------------------------------------------------------------ the seek of a table scan
+// A sorted table's key columns are a Cols type: Cols::Key with lt(a, b), the table's byte order (host and
+// device), and next(k, &out), the key after k (host; false past the last key); Cols::at(i) is row i's key
+// (device).  The Z tables' is ZCols (gm_filter.hip), the attribute table's AttrCols (gm_attr_table.hip).  SeekRange,
+// merge_ranges and the attribute key are gm_seek.hpp's, which a host compiler takes alone.
+// row interval of each range: [first row >= lo, first row > hi)
+template <class Cols>
+__global__ __launch_bounds__(FTPB) void k_range_bounds(Cols c, int64_t n, const SeekRange<typename Cols::Key>* __restrict__ rg,
+                                                       int64_t nr, int64_t* __restrict__ start, int64_t* __restrict__ len) {
+  using Key = typename Cols::Key;
+  const int64_t r = (int64_t)blockIdx.x * FTPB + threadIdx.x;
+  if (r >= nr) return;
+  const SeekRange<Key> q = rg[r];
+  int64_t lo = 0, hi = n;  // lower_bound(lo key)
+  while (lo < hi) {
+    const int64_t m = (lo + hi) >> 1;
+    if (Key::lt(c.at(m), q.lo)) lo = m + 1; else hi = m;
+  }
+  const int64_t a = lo;
+  hi = n;  // upper_bound(hi key)
+  while (lo < hi) {
+    const int64_t m = (lo + hi) >> 1;
+    if (!Key::lt(q.hi, c.at(m))) lo = m + 1; else hi = m;
+  }
+  start[r] = a;
+  len[r] = lo - a;
+}
+
+// the merged ranges to the device and their row intervals: start[nr], and the lengths in coff[nr] (+ 1 entry
+// for scan_candidates' total)
+template <class Cols>
+int seek_ranges(gm_ctx* ctx, DevTemps& tmp, const Cols& c, int64_t n, const std::vector<SeekRange<typename Cols::Key>>& rg,
+                int64_t** start, int64_t** coff) {
+  using R = SeekRange<typename Cols::Key>;
+  const int64_t nr = (int64_t)rg.size();
+  R* d_rg = nullptr;
+  int rc = tmp.alloc_async((size_t)nr * sizeof(R), &d_rg);
+  if (!rc) rc = tmp.alloc_async((size_t)nr * 8, start);
+  if (!rc) rc = tmp.alloc_async((size_t)(nr + 1) * 8, coff);
+  if (!rc) rc = copy_h2d(ctx, d_rg, rg.data(), (size_t)nr * sizeof(R));
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_range_bounds<Cols>, dim3((unsigned)((nr + FTPB - 1) / FTPB)), dim3(FTPB), 0, ctx->stream, c, n,
+                     (const R*)d_rg, nr, *start, *coff);
+  GM_CHECK_LAUNCH();
+  return GM_OK;
+}
+
+// The row filter the tablet server runs on the key (k_range_mask, gm_filter.hip): none, Z3Filter.inBounds on
+// (bin, z) or Z2Filter.inBounds on z, with its descriptor words and the key columns it reads.
+enum : int { RF_NONE = 0, RF_Z3 = 1, RF_Z2 = 2 };
+struct RowFilter {
+  int rf, nxy;
+  const std::vector<int32_t>* words;
+  const uint16_t* bin;
+  const uint64_t* z;
+};
+// the full filter's own argument rules (gm_scan_filter): boxes with their envelope columns, during with t_ms
+inline bool full_filter_ok(const gm_scan_filter* f) {
+  const bool env = f->n_boxes > 0;
+  return !(f->n_boxes < 0 || (env && (!f->boxes || !f->xmin || !f->ymin || !f->xmax || !f->ymax)) || (f->during != 0 && !f->t_ms));
+}
+// a scan without rows or ranges
+inline int no_candidates(int64_t* n_match, int64_t* n_scanned, int64_t* n_envelope) {
+  if (n_match) *n_match = 0;
+  if (n_scanned) *n_scanned = 0;
+  if (n_envelope) *n_envelope = 0;
+  return GM_OK;
+}
+// after seek_ranges: the candidate count (*n_scanned), the mask pass over the candidates (row filter, full
+// filter; with geom the exact refine, hq: the query polygons), the compaction, ids through perm.  Synchronises.
+int scan_candidates(gm_ctx* ctx, DevTemps& tmp, const int64_t* start, int64_t* coff, int64_t nr,
+                    const gm_scan_filter* f, const RowFilter& row_filter, const gm_geom_column* geom,
+                    const polyq::HostQuery* hq, const int64_t* perm, int64_t* ids, int64_t ids_cap, int64_t* n_match,
+                    int64_t* n_scanned, int64_t* n_envelope);
 
 // JTS Envelope.intersects(Envelope): false for a null envelope (maxx < minx) on either side
 __device__ __forceinline__ bool env_intersects(double ax0, double ay0, double ax1, double ay1, const double* q) {

@@ -1171,6 +1171,90 @@ int gm_hist_merge(gm_hist_state* a, int64_t* a_counts, const gm_hist_state* b, c
 int gm_gen_points(gm_ctx* ctx, uint64_t seed, int64_t n, int64_t index_base, double lon0, double lon1,
                   double lat0, double lat1, int64_t t0, int64_t t1, double* x, double* y, int64_t* t_ms);
 
+/* ------------------------------------------------------------------ attribute index table */
+/* The attribute index (`attr`, version 8; att/ = idx/index/attribute/) of an attribute with index=true
+   (AttributeIndex.defaults, att/AttributeIndex.scala:84-95) for the fixed-width bindings.  A row is
+   [shard 1 B, if sharded][UTF-8 of the lexicoded value][0x00][tier bytes][feature id]
+   (AttributeIndexKeySpace.toIndexKey, att/AttributeIndexKeySpace.scala:68-137); a null attribute writes no
+   row.  The tier is the secondary key space the index was created with (att/AttributeIndex.scala:49-69):
+     GM_ATTR_TIER_NONE  no tier bytes
+     GM_ATTR_TIER_DATE  ByteArrays.toOrderedBytes(dtg ms): 8 B, sign bit flipped, big-endian; a null date is
+                        Long.MinValue (att/DateIndexKeySpace.scala:48-56)
+     GM_ATTR_TIER_Z3    [bin BE16][z BE64] of Z3IndexKeySpace.toIndexKey without its shard
+                        (idx/index/z3/Z3IndexKeySpace.scala:63-95)
+   The lexicoders.  AttributeIndexKey.typeEncode (att/AttributeIndexKey.scala:41,67) delegates to
+   org.calrissian.mango 3.0.0 LexiTypeEncoders, which is outside the reference tree; this table is the
+   definition here.  The key text is the ordered value v in lower-case hex digits, zero padded:
+     Integer                       GM_ATTR_INT32    v = (uint32)(x ^ 0x80000000)              8 digits
+     Long; Date, Timestamp (ms)    GM_ATTR_INT64    v = (uint64)(x ^ 0x8000000000000000)      16 digits
+     Float                         GM_ATTR_FLOAT32  b = floatToIntBits(x) (every NaN 0x7fc00000);
+                                                    v = b < 0 ? ~b : b ^ 0x80000000           8 digits
+     Double                        GM_ATTR_FLOAT64  the same over doubleToLongBits            16 digits
+   The Integer row is pinned by the reference's DefaultSplitterTest.scala:134-188 ("80000000", "8000000c",
+   "7ffffff7").  Long, Float and Double are PARITY UNPINNED: nothing in the reference tree states their text.
+   By the definition the byte order of the key text is the unsigned order of v; -0.0 sorts immediately below
+   +0.0 and is a different key; NaN sorts above +infinity.
+   Not built, GM_E_INVALID with a gm_last_error text: GM_ATTR_UTF8 (String: variable-length keys), List
+   attributes, the XZ3 / Z2 / XZ2 tiers, the legacy index versions (legacy/AttributeIndexV2-V7), the join
+   index and attribute-level visibility.
+   Every entry takes the context and runs on its stream.  gm_attr_key_bytes only enqueues (asynchronous); the
+   other three synchronise the context stream. */
+#define GM_ATTR_TIER_NONE 0
+#define GM_ATTR_TIER_DATE 1
+#define GM_ATTR_TIER_Z3 2
+
+/* toIndexKey's value part (att/AttributeIndexKeySpace.scala:112-117) over a column, its validity and
+   validity_offset honoured: v_out (device, n entries) receives the ordered value of every NON-NULL slot in
+   input order, rows_out (device, n entries) that slot's input row, *n_rows (host) their number; the entries
+   past *n_rows are not written.  A null slot produces nothing (:113-114).  values need natural alignment,
+   v_out and rows_out 8 B.  Synchronises the context stream: the row count is read back. */
+int gm_attr_index_key(gm_ctx* ctx, const gm_attr_column* col, int64_t n, uint64_t* v_out, int64_t* rows_out,
+                      int64_t* n_rows);
+
+/* The row-key prefix of m table rows (att/AttributeIndexKeySpace.scala:116-134): out (device) gets
+   m * key_len bytes, [shard, if shard != NULL][hex text of v: 8 B for the 32-bit types, else 16][0x00][tier].
+   tier_kind GM_ATTR_TIER_DATE: t = epoch ms, 8 B; GM_ATTR_TIER_Z3: bin and t = z, 10 B; GM_ATTR_TIER_NONE: bin
+   and t are not read.  key_len is constant per table, 9 to 28.  Asynchronous. */
+int gm_attr_key_bytes(gm_ctx* ctx, int type, const uint8_t* shard, const uint64_t* v, int tier_kind,
+                      const int16_t* bin, const int64_t* t, int64_t m, uint8_t* out);
+
+/* Sorts the key columns into table order, the byte order of the rows above: shard, then v unsigned, then the
+   tier -- bin as u16 then t as u64 (Z3: t = z; date: t = the ordered long, ms ^ 2^63, bin NULL; no tier: bin
+   and t NULL).  Stable: rows of equal keys keep their input order, which stands for the feature id the store
+   appends.  perm_out[i] = the input row of table row i.  shard / shard_out, bin / bin_out and t / t_out are
+   each NULL together; bin needs t.  m < 2^32.  With a tier this is two stable gm_sort_keys passes, by tier
+   and by (shard, v), with a gather between them and the permutations composed: device temporaries are
+   gm_sort_keys's and 32 B per row from the stream's pool (+ 2 B with a bin, + 1 B with a shard).  Without a
+   tier it is one gm_sort_keys.  Synchronises the context stream, as gm_sort_keys does. */
+int gm_attr_sort(gm_ctx* ctx, const uint8_t* shard, const uint64_t* v, const int16_t* bin, const int64_t* t, int64_t m,
+                 uint8_t* shard_out, uint64_t* v_out, int16_t* bin_out, int64_t* t_out, int64_t* perm_out);
+
+/* A scan range over the key prefix, inclusive at both ends, compared lexicographically as (shard, v, b, t),
+   every field unsigned: what getRangeBytes and the tier combination make of a query
+   (att/AttributeIndexKeySpace.scala:150-190, 224-343; idx/api/GeoMesaFeatureIndex.scala:298-356), one per
+   shard.  The fields of a column the table does not have (b without the Z3 tier, t without a tier) are not
+   compared. */
+typedef struct {
+  uint64_t v_lo, v_hi;   /* ordered attribute value */
+  uint64_t t_lo, t_hi;   /* tier low word: z, or the ordered date; 0 / all ones without a tier */
+  uint16_t b_lo, b_hi;   /* tier high word: bin (Z3 tier); 0 / 0xffff otherwise */
+  uint8_t  shard;
+  uint8_t  reserved[3];
+} gm_attr_range;
+
+/* Seek-and-filter over a sorted attribute table (gm_attr_sort order).  The ranges (host array) are merged as
+   gm_table_scan merges them, each one's row interval is found by binary search on the composite key, and the
+   secondary filter runs on every candidate through gm_scan_filter's full filter: n_boxes > 0 with xmin = xmax
+   = the features' x and ymin = ymax = y is, for point features, GeoTools BBOX (inclusive); during tests t_ms
+   in (t_lo, t_hi), exclusive; rows maps a table row to its column row, else perm does.  A filter with
+   z3filter, z2filter or polys is GM_E_INVALID here.  ids (device, optional) receives the matching rows in
+   table order, mapped through perm (device, optional) to input rows; *n_match / *n_scanned (host) the match
+   and candidate counts.  GM_E_CAPACITY, the NULL rules, ids_cap < 0 (GM_E_INVALID) and the synchronisation are
+   gm_table_scan's; v, t, perm and ids need 8-B alignment. */
+int gm_attr_table_scan(gm_ctx* ctx, const uint8_t* shard, const uint64_t* v, const int16_t* bin, const int64_t* t,
+                       int64_t m, const gm_attr_range* ranges, int64_t n_ranges, const gm_scan_filter* f,
+                       const int64_t* perm, int64_t* ids, int64_t ids_cap, int64_t* n_match, int64_t* n_scanned);
+
 #ifdef __cplusplus
 }
 #endif
